@@ -7,7 +7,11 @@ Workload at N=1 = BASELINE.json configs[2]: large-v3 dims, batch = 8 x 30 s, gre
 count is fixed: `sample_len` forced tokens per clip with EOT suppressed, so the work is
 identical run to run.  Inputs are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the timed path computed in its last step (the last decode chain of rank 0: token ids,
+sum of log-probabilities and no-speech probability per row, what a caller of HipTask.greedy receives) as DIR/<name>.npy
+in float64 / float32, so that two builds can be compared output for output on identical, seeded inputs.
 
 Schedule (round 6): the K passes of --batch clips are COALESCED, --chain-batches (3) at a time, into decode chains of up to 24 rows —
 one task, one prompt pass, one decode step per token for all of them, the decoder's weights streamed once per step for 24 clips
@@ -105,6 +109,8 @@ def parse():
                                                                 "projection kernels take up to 24 rows)")
     p.add_argument("--in-flight", type=int, default=1, help="decode chains in flight at once on this GPU, each on its own task and HIP stream, all driven "
                                                             "from one host thread; clips resident = --batch x --chain-batches x --in-flight")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
     p.add_argument("--extras-in-flight", type=int, default=3, help="chains in flight in the `in_flight` variants of the extra legs (beam search, base x 1, turbo)")
     return p.parse_args()
 
@@ -284,7 +290,9 @@ def main():
             toks[:, :T0] = init_t
             if begin_only:
                 return tk.greedy_begin(toks, params, sot_index, tok.no_speech)
-            return tk.greedy(toks, params, sot_index, tok.no_speech)[0]
+            return tk.greedy(toks, params, sot_index, tok.no_speech)
+
+    last_chain = {}     # outputs of the last chain of the latest run_passes: token buffer + greedy's (n, sum_logprobs, no_speech_probs)
 
     def run_passes(k):
         """k passes of B clips as chains of up to CB passes, up to F chains in flight; returns the token count of the last chain"""
@@ -292,17 +300,21 @@ def main():
         n = 0
         if F == 1:
             for nb in sizes:
-                n = enqueue_chain(lanes[0], nb, False)
+                res = enqueue_chain(lanes[0], nb, False)
+                n = res[0]
+            last_chain.update(tokens=lanes[0].tokens[sizes[-1]], result=res)
             return n
         pend, nxt = [None] * F, 0
         while nxt < len(sizes) or any(p is not None for p in pend):
             for i in range(F):
                 if pend[i] is None and nxt < len(sizes):
-                    pend[i] = enqueue_chain(lanes[i], sizes[nxt], True)
+                    pend[i] = (enqueue_chain(lanes[i], sizes[nxt], True), nxt)
                     nxt += 1
                 elif pend[i] is not None:
-                    res = pend[i].poll()
+                    res = pend[i][0].poll()
                     if res is not None:
+                        if pend[i][1] == len(sizes) - 1:
+                            last_chain.update(tokens=lanes[i].tokens[sizes[-1]], result=res)
                         n, pend[i] = res[0], None
         return n
 
@@ -329,6 +341,8 @@ def main():
         return n, time.perf_counter() - t_start
 
     n_tok, elapsed = timed_region()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_chain, n_tok)
     per_rank_ms = [elapsed / args.steps * 1e3]
     if dist is not None:
         mine = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -674,6 +688,19 @@ def main():
     if dist is not None:
         dist.barrier()                      # rank 0 measures its kernel table after the timed region: leave together
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir: str, last_chain: dict, n_tok: int) -> None:
+    """--dump-outputs: the last timed chain's results as .npy (token ids exact in float64; a few KB in all)"""
+    toks = last_chain["tokens"][:, :n_tok].cpu().numpy().astype(np.float64)
+    _, sum_lp, nsp = last_chain["result"]
+    arrays = {"tokens": toks, "sum_logprobs": sum_lp.cpu().numpy().astype(np.float32)}
+    if nsp is not None:
+        arrays["no_speech_probs"] = nsp.cpu().numpy().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"outputs of the last timed step: {', '.join(f'{k} {v.shape}' for k, v in arrays.items())} -> {out_dir}")
 
 
 def chain_schedule(args, world: int) -> dict:

@@ -2,7 +2,7 @@
 libwhisper_audio.so) and the RIFF/WAVE reader behind whisper_amd.load_audio.  CPU only.
 
 The decoder verifies every frame's CRC-8 / CRC-16 and the STREAMINFO MD5 of the decoded PCM, so a successful decode
-of a third-party file (tests/jfk.flac of the reference, 24-bit stereo 44.1 kHz, LPC + Rice coded) is self-validating;
+of a third-party stream (the head of tests/jfk.flac of the reference, 24-bit stereo 44.1 kHz, LPC + Rice coded) is self-validating;
 the bit-level paths are additionally exercised with FLAC streams written by the small encoder below (VERBATIM,
 CONSTANT and FIXED-predictor subframes with Rice residuals, independent / left-side / mid-side stereo)."""
 import hashlib
@@ -15,7 +15,8 @@ import pytest
 
 from whisper_amd import audio as A
 
-JFK = "/root/reference/tests/jfk.flac"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+JFK = os.path.join(GOLDEN, "jfk_head.flac")      # first 16 frames of the reference's tests/jfk.flac (tests/golden/make_golden_flac.py)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -219,20 +220,25 @@ def test_wav_extensible_and_malformed_headers(tmp_path, monkeypatch):
             A.load_audio(q)
 
 
-@pytest.mark.reference
 def test_jfk_flac_decodes_and_matches_reference_test_invariants():
-    """tests/jfk.flac of the reference: decodes (CRCs + MD5 signature verified inside the decoder) to the PCM whose
-    SHA-256 is pinned below, and load_audio meets the asserts of the reference's tests/test_audio.py:10-19"""
-    if not os.path.isfile(JFK):
-        pytest.skip("reference checkout not present")
+    """the head of tests/jfk.flac of the reference, its frames byte for byte (tests/golden/jfk_head.flac): decodes (CRCs +
+    MD5 signature verified inside the decoder) to the PCM whose SHA-256 is pinned below (the prefix of the whole file's
+    PCM, itself verified against the encoder's MD5), and load_audio meets the asserts of the reference's
+    tests/test_audio.py:10-19 on it: mono, 16 kHz, the same samples as load_audio of the whole file
+    (tests/golden/jfk_tiny_en.npz) up to the resampler's edge at the cut"""
     with open(JFK, "rb") as f:
         pcm, rate, bps = A.decode_flac(f.read())
-    assert (pcm.shape, rate, bps) == ((485100, 2), 44100, 24)
-    assert hashlib.sha256(pcm.astype("<i4").tobytes()).hexdigest() == JFK_PCM_SHA256
+    assert (pcm.shape, rate, bps) == ((JFK_HEAD_SAMPLES, 2), 44100, 24)
+    assert hashlib.sha256(pcm.astype("<i4").tobytes()).hexdigest() == JFK_HEAD_PCM_SHA256
     audio = A.load_audio(JFK)
     assert audio.ndim == 1
-    assert A.SAMPLE_RATE * 10 < audio.shape[0] < A.SAMPLE_RATE * 12
+    assert audio.shape[0] == -(-JFK_HEAD_SAMPLES * A.SAMPLE_RATE // 44100)
     assert 0 < audio.std() < 1
+    whole = np.load(os.path.join(GOLDEN, "jfk_tiny_en.npz"))["jfk_pcm16"]         # load_audio of the whole file
+    assert whole.shape[0] == 11 * A.SAMPLE_RATE
+    n = audio.shape[0] - 16
+    assert np.array_equal(np.round(audio[:n] * 32768.0).astype(np.int16), whole[:n])
 
 
-JFK_PCM_SHA256 = "c7741f92548994acaee42e83e128e4f1ec59e9fd47e2c4c886c37a33ec021521"
+JFK_HEAD_SAMPLES = 16 * 4608
+JFK_HEAD_PCM_SHA256 = "ff90dee6493d1852c12693cadbec54378a3c57ad9710418376c07816356c1c67"

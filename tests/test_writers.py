@@ -1,18 +1,15 @@
 """The result writers (txt / vtt / srt / tsv / json) against the reference's on randomly
-generated transcripts with word timings, for every combination of the subtitle layout options.  CPU only; needs the
-reference checkout (build container)."""
+generated transcripts with word timings, for every combination of the subtitle layout options.  CPU only; the reference's
+outputs are stored in tests/golden/writers_reference.pt.gz (tests/refgolden.py, tests/golden/make_golden_host.py)."""
 import io
 import itertools
 import json
-import os
 import random
-import sys
 
 import pytest
+from refgolden import raises, store_fixture
 
 from whisper_amd import utils as U
-
-REF = "/root/reference"
 
 
 def _result(seed, with_words=True):
@@ -39,40 +36,61 @@ def _result(seed, with_words=True):
     return {"text": "".join(s["text"] for s in segments), "segments": segments, "language": "en"}
 
 
-@pytest.fixture(scope="module")
-def ref_utils():
-    if not os.path.isdir(os.path.join(REF, "whisper")):
-        pytest.skip("reference checkout not present")
-    sys.path[:0] = [os.path.join(os.path.dirname(__file__), "shims"), REF]
-    import whisper.utils as RU
-    return RU
+_store = store_fixture("writers_reference")
 
 
-@pytest.mark.reference
-def test_writers_match_reference(ref_utils, tmp_path):
+@pytest.fixture
+def ref_utils(_store):
+    """the reference's whisper.utils while recording; None otherwise (it is only read inside expect(...))"""
+    return None if _store.ref is None else _store.ref.utils
+
+
+@pytest.fixture
+def expect(_store, request):
+    return _store.expect_for(request.node.name)
+
+
+def test_writers_match_reference(ref_utils, expect, tmp_path):
     grids = list(itertools.product([None, 12, 28, 60], [None, 1, 2, 3], [False, True], [None, 1, 3, 5]))
     for seed in range(12):
         for with_words in (True, False):
             res = _result(seed, with_words)
             for fmt in ("txt", "vtt", "srt", "tsv", "json"):
-                for width, lines, hl, per_line in (grids if fmt in ("vtt", "srt") else grids[:1]):
+                cases = grids if fmt in ("vtt", "srt") else grids[:1]
+
+                def theirs():
+                    outs = []
+                    for width, lines, hl, per_line in cases:
+                        kw = dict(max_line_width=width, max_line_count=lines, highlight_words=hl, max_words_per_line=per_line)
+                        out = io.StringIO()
+                        ref_utils.get_writer(fmt, str(tmp_path)).write_result(res, file=out, options=dict(kw))
+                        outs.append(out.getvalue())
+                    return outs
+                for (width, lines, hl, per_line), theirs_text in zip(cases, expect(theirs), strict=True):
                     kw = dict(max_line_width=width, max_line_count=lines, highlight_words=hl, max_words_per_line=per_line)
-                    mine, theirs = io.StringIO(), io.StringIO()
+                    mine = io.StringIO()
                     U.get_writer(fmt, str(tmp_path)).write_result(res, file=mine, options=dict(kw))
-                    ref_utils.get_writer(fmt, str(tmp_path)).write_result(res, file=theirs, options=dict(kw))
-                    assert mine.getvalue() == theirs.getvalue(), (seed, with_words, fmt, kw)
+                    assert mine.getvalue() == theirs_text, (seed, with_words, fmt, kw)
     # keyword arguments instead of the options dict, and the file-naming __call__ / "all" paths
     res = _result(99)
-    a, b = io.StringIO(), io.StringIO()
+    a = io.StringIO()
     U.WriteSRT(str(tmp_path)).write_result(res, file=a, max_line_width=20, max_line_count=2, highlight_words=True)
-    ref_utils.WriteSRT(str(tmp_path)).write_result(res, file=b, max_line_width=20, max_line_count=2, highlight_words=True)
-    assert a.getvalue() == b.getvalue()
+
+    def theirs_srt():
+        b = io.StringIO()
+        ref_utils.WriteSRT(str(tmp_path)).write_result(res, file=b, max_line_width=20, max_line_count=2, highlight_words=True)
+        return b.getvalue()
+    assert a.getvalue() == expect(theirs_srt)
     (tmp_path / "mine").mkdir()
-    (tmp_path / "ref").mkdir()
     U.get_writer("all", str(tmp_path / "mine"))(res, "/some/dir/clip.flac", {"max_line_width": 30, "max_line_count": 2})
-    ref_utils.get_writer("all", str(tmp_path / "ref"))(res, "/some/dir/clip.flac", {"max_line_width": 30, "max_line_count": 2})
+
+    def theirs_files():
+        (tmp_path / "ref").mkdir()
+        ref_utils.get_writer("all", str(tmp_path / "ref"))(res, "/some/dir/clip.flac", {"max_line_width": 30, "max_line_count": 2})
+        return {ext: (tmp_path / "ref" / f"clip.{ext}").read_text(encoding="utf-8") for ext in ("txt", "vtt", "srt", "tsv", "json")}
+    theirs_all = expect(theirs_files)
     for ext in ("txt", "vtt", "srt", "tsv", "json"):
-        assert (tmp_path / "mine" / f"clip.{ext}").read_text(encoding="utf-8") == (tmp_path / "ref" / f"clip.{ext}").read_text(encoding="utf-8")
+        assert (tmp_path / "mine" / f"clip.{ext}").read_text(encoding="utf-8") == theirs_all[ext]
 
 
 def test_writers_known_output():
@@ -102,34 +120,32 @@ def test_writers_known_output():
         U.get_writer("docx", ".")
 
 
-@pytest.mark.reference
-def test_small_helpers_match_reference(ref_utils):
+def test_small_helpers_match_reference(ref_utils, expect):
     """exact_div, compression_ratio, format_timestamp, get_start / get_end (utils.py:24-82) on random inputs"""
     RU = ref_utils
     rnd = random.Random(9)
     for _ in range(200):
         y, k = rnd.randint(1, 50), rnd.randint(0, 99)
-        assert U.exact_div(y * k, y) == RU.exact_div(y * k, y) == k
+        assert U.exact_div(y * k, y) == expect(lambda: RU.exact_div(y * k, y)) == k
     for x, y in ((480000, 160), (3000, 2), (0, 7)):
-        assert U.exact_div(x, y) == RU.exact_div(x, y)
+        assert U.exact_div(x, y) == expect(lambda: RU.exact_div(x, y))
     for bad in ((10, 3), (7, 2)):
         with pytest.raises(AssertionError):
             U.exact_div(*bad)
-        with pytest.raises(AssertionError):
-            RU.exact_div(*bad)
+        assert expect(lambda: raises(AssertionError, lambda: RU.exact_div(*bad))) is not None
     words = ["the", "quick", "über", "naïve", "日本語", "a", " ", "\n", "and and and and"]
     for _ in range(100):
         text = " ".join(rnd.choice(words) for _ in range(rnd.randint(1, 60)))
-        assert U.compression_ratio(text) == RU.compression_ratio(text)
+        assert U.compression_ratio(text) == expect(lambda: RU.compression_ratio(text))
     for _ in range(300):
         s = rnd.choice([0.0, rnd.uniform(0, 70), rnd.uniform(3500, 3700), rnd.uniform(0, 1e5), 59.9996, 3599.9999])
         for hours, mark in ((False, "."), (True, ","), (False, ","), (True, ".")):
-            assert U.format_timestamp(s, hours, mark) == RU.format_timestamp(s, hours, mark)
+            assert U.format_timestamp(s, hours, mark) == expect(lambda: RU.format_timestamp(s, hours, mark))
     with pytest.raises(AssertionError):
         U.format_timestamp(-1.0)
     for seed in range(40):
         segs = _result(seed)["segments"]                  # both index s["words"]: word-timed segments only
-        assert U.get_start(segs) == RU.get_start(segs) and U.get_end(segs) == RU.get_end(segs)
+        assert (U.get_start(segs), U.get_end(segs)) == expect(lambda: (RU.get_start(segs), RU.get_end(segs)))
         empty = [dict(s, words=[]) for s in segs]
-        assert U.get_start(empty) == RU.get_start(empty) and U.get_end(empty) == RU.get_end(empty)
-    assert U.get_start([]) == RU.get_start([]) and U.get_end([]) == RU.get_end([])
+        assert (U.get_start(empty), U.get_end(empty)) == expect(lambda: (RU.get_start(empty), RU.get_end(empty)))
+    assert (U.get_start([]), U.get_end([])) == expect(lambda: (RU.get_start([]), RU.get_end([])))
