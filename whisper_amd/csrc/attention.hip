@@ -478,10 +478,12 @@ __global__ __launch_bounds__(WAVES * 64) void attn_decode_kernel(whk::DecAttnArg
   // zero-fill else-arm would make the compiler drain vmcnt at every join).  Rounds >= nround are skipped by a
   // wave-uniform branch; slots past the split inside a live round are neutralised by score = -inf.
   const int kk0 = wave * KPW + ks;
-  const int klast = nkeys > 0 ? nkeys - 1 : 0;
+  // an empty split (Tk < splits, or rounded chunks that end before the last split) has k0 >= Tk: its loads clamp to key 0,
+  // as in the matrix-core group kernels — never to key k0, which lies past the end of the K / V rows
+  const int kclamp = nkeys > 0 ? k0 + nkeys - 1 : 0;
   const uint32_t ldk = (uint32_t)a.k_ld, ldv = (uint32_t)a.v_ld;
-  const uint32_t ok0 = (uint32_t)(k0 + kk0) * ldk, okl = (uint32_t)(k0 + klast) * ldk;
-  const uint32_t ov0 = (uint32_t)(k0 + kk0) * ldv, ovl = (uint32_t)(k0 + klast) * ldv;
+  const uint32_t ok0 = (uint32_t)(k0 + kk0) * ldk, okl = (uint32_t)kclamp * ldk;
+  const uint32_t ov0 = (uint32_t)(k0 + kk0) * ldv, ovl = (uint32_t)kclamp * ldv;
   unit_t ku[NL], vu[NL];
 #pragma unroll
   for (int i = 0; i < NL; ++i) {
@@ -680,10 +682,10 @@ __global__ __launch_bounds__(WAVES * 64) void attn_decode_group_kernel(whk::DecA
   }
   asm volatile("" ::: "memory");
   const int kk0 = wave * KPW + ks;
-  const int klast = nkeys > 0 ? nkeys - 1 : 0;
+  const int kclamp = nkeys > 0 ? k0 + nkeys - 1 : 0;                 // empty split: key 0 (attn_decode_kernel above)
   const uint32_t ldk = (uint32_t)a.k_ld, ldv = (uint32_t)a.v_ld;
-  const uint32_t ok0 = (uint32_t)(k0 + kk0) * ldk, okl = (uint32_t)(k0 + klast) * ldk;
-  const uint32_t ov0 = (uint32_t)(k0 + kk0) * ldv, ovl = (uint32_t)(k0 + klast) * ldv;
+  const uint32_t ok0 = (uint32_t)(k0 + kk0) * ldk, okl = (uint32_t)kclamp * ldk;
+  const uint32_t ov0 = (uint32_t)(k0 + kk0) * ldv, ovl = (uint32_t)kclamp * ldv;
   unit_t ku[NL], vu[NL];
 #pragma unroll
   for (int i = 0; i < NL; ++i) {
@@ -1201,6 +1203,7 @@ template <typename T>
 static hipError_t launch_attn_decode_t(const DecAttnArgs& a, hipStream_t stream) {
   constexpr int KPW = ET<T>::UNIT;                 // keys per wave-load: 64 lanes / (64 / UNIT lanes per key)
   if (a.d_len) {
+    whk::g_form = sizeof(T) == 2 ? "attn/self<half>" : "attn/self<float>";
     dim3 grid(a.splits, a.H, a.R), block(8 * 64);
     hipLaunchKernelGGL((attn_decode_kernel<T, 8, 8, true>), grid, block, 0, stream, a);
     return hipGetLastError();
@@ -1213,17 +1216,24 @@ static hipError_t launch_attn_decode_t(const DecAttnArgs& a, hipStream_t stream)
       dim3 ggrid(a.splits, a.H, a.R / a.kv_group);
       // round 6: whole cache lines per request (the diagonal tile); A/B against the kernels below: WH_GROUP_ATTN_HALF_LINES=1
       if (!WH_DEV_FLAG("WH_GROUP_ATTN_HALF_LINES") && a.vt_ld >= 64) {
+        whk::g_form = "attn/group_diag";
         hipLaunchKernelGGL((attn_decode_group_diag_kernel<8>), ggrid, dim3(512), 0, stream, a);
         return hipGetLastError();
       }
       // 8 waves x 2 blocks and 4 waves x 4 blocks of 32 keys measured the same (232.8 vs 233.0 ms per 64-step beam pass)
-      if ((chunk + 127) / 128 <= 1) hipLaunchKernelGGL((attn_decode_group_mfma_kernel<1, 8>), ggrid, dim3(512), 0, stream, a);
-      else hipLaunchKernelGGL((attn_decode_group_mfma_kernel<2, 8>), ggrid, dim3(512), 0, stream, a);
+      if ((chunk + 127) / 128 <= 1) {
+        whk::g_form = "attn/group_mfma<1>";
+        hipLaunchKernelGGL((attn_decode_group_mfma_kernel<1, 8>), ggrid, dim3(512), 0, stream, a);
+      } else {
+        whk::g_form = "attn/group_mfma<2>";
+        hipLaunchKernelGGL((attn_decode_group_mfma_kernel<2, 8>), ggrid, dim3(512), 0, stream, a);
+      }
       return hipGetLastError();
     }
   }
   if (a.kv_group > 1 && a.kv_group <= 8 && a.R % a.kv_group == 0 && chunk <= 8 * 8 * KPW) {
     // beam groups: one workgroup per (split, head, audio) scores all beams against one K/V tile
+    whk::g_form = sizeof(T) == 2 ? "attn/group<half>" : "attn/group<float>";
     dim3 ggrid(a.splits, a.H, a.R / a.kv_group), gblock(8 * 64);
     hipLaunchKernelGGL((attn_decode_group_kernel<T, 8, 8, 8>), ggrid, gblock, 0, stream, a);
     return hipGetLastError();
@@ -1231,8 +1241,11 @@ static hipError_t launch_attn_decode_t(const DecAttnArgs& a, hipStream_t stream)
   dim3 grid(a.splits, a.H, a.R), block(4 * 64);
   const int rounds = (chunk + 4 * KPW - 1) / (4 * KPW);
   if (rounds > 16) return hipErrorInvalidValue;
-  if (rounds <= 8) hipLaunchKernelGGL((attn_decode_kernel<T, 8, 4, false>), grid, block, 0, stream, a);
-  else if (rounds <= 12) hipLaunchKernelGGL((attn_decode_kernel<T, 12, 4, false>), grid, block, 0, stream, a);
+  const int nl = rounds <= 8 ? 8 : rounds <= 12 ? 12 : 16;
+  whk::g_form = sizeof(T) == 2 ? (nl == 8 ? "attn/rounds<half,8>" : nl == 12 ? "attn/rounds<half,12>" : "attn/rounds<half,16>")
+                               : (nl == 8 ? "attn/rounds<float,8>" : nl == 12 ? "attn/rounds<float,12>" : "attn/rounds<float,16>");
+  if (nl == 8) hipLaunchKernelGGL((attn_decode_kernel<T, 8, 4, false>), grid, block, 0, stream, a);
+  else if (nl == 12) hipLaunchKernelGGL((attn_decode_kernel<T, 12, 4, false>), grid, block, 0, stream, a);
   else hipLaunchKernelGGL((attn_decode_kernel<T, 16, 4, false>), grid, block, 0, stream, a);
   return hipGetLastError();
 }

@@ -500,6 +500,7 @@ __global__ __launch_bounds__(1024) void gemm_f16_rows_kernel(whk::GemmArgs p) {
 
 template <int ACT, int BIAS>
 hipError_t launch_rows(const whk::GemmArgs& a, int batch, hipStream_t stream) {
+  whk::g_form = WH_FORM_NAME("gemm/rows<%d,%d>", ACT, BIAS);
   whk::GemmArgs p = a;
   p.tiles_m = (p.M + 255) / 256;
   p.tiles_n = (p.N + 255) / 256;
@@ -542,6 +543,7 @@ hipError_t launch_shape(const whk::GemmArgs& a, int batch, hipStream_t stream) {
   constexpr int BM = WGM * FM * 16, BN = WGN * FN * 16;
   constexpr int LDS = NS * (BM + BN) * 128;
   static_assert(LDS <= 160 * 1024, "LDS ring does not fit");
+  whk::g_form = WH_FORM_NAME("gemm/tile<%s,%s,%d,%d>", sizeof(T) == 2 ? "half" : "float", sizeof(OutT) == 2 ? "half" : "float", WGM, WGN);
   whk::GemmArgs p = a;
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.N + BN - 1) / BN;

@@ -470,6 +470,8 @@ hipError_t launch_cfg(const whk::GemvArgs& a, int gp, hipStream_t stream) {
 template <typename T, int RT, int LPR, bool MULTI, int WAVES, int GS, bool MF = false>
 hipError_t launch_pro(const whk::GemvArgs& a, int gp, hipStream_t stream) {
   constexpr int TPR = WAVES * 64 / RT;
+  whk::g_form = WH_FORM_NAME("%s<%s,%d>/pro<%d,%d,%d,%d>", MF ? "rows16_mf" : "rt", sizeof(T) == 2 ? "half" : "float", RT, LPR,
+                             (int)MULTI, WAVES, GS);
   switch (a.pro) {
     case whk::PRO_PLAIN: {
       const int upr = a.K / ET<T>::UNIT;            // J = 16-byte units per thread per row
@@ -727,6 +729,7 @@ hipError_t launch_stream(const whk::GemvArgs& a, hipStream_t stream) {
   constexpr int UNIT = ET<T>::UNIT;
   static_assert(RT <= 8, "one lane per row in the store epilogue");
   if (a.pro != whk::PRO_LN || a.epi != whk::EPI_F32 || a.K % (8 * UNIT) != 0 || a.K > 256 * 8) return hipErrorInvalidValue;
+  whk::g_form = WH_FORM_NAME("stream<%s,%d>", sizeof(T) == 2 ? "half" : "float", RT);
   const size_t lds = (size_t)RT * a.K * sizeof(T);
   const int ngroups = (a.N + 7) / 8;
   // ~2 waves per SIMD over the whole chip: 256 CUs x 2 workgroups x 8 waves
@@ -1110,6 +1113,8 @@ hipError_t launch_gemv8_nrt(const whk::GemvArgs& a, int fw, hipStream_t stream) 
   constexpr int WAVES = GS * KS + XW;
   static_assert(WAVES <= 16, "at most 1024 threads per workgroup");
   if (fw < 1 || fw > 8 * GS) return hipErrorInvalidValue;
+  whk::g_form = WH_FORM_NAME("gemv8/%s/gs%d/ks%d/xw%d/rt%d", PRO == whk::PRO_PLAIN ? "plain" : PRO == whk::PRO_LN ? "LN" :
+                             CSm == 2 ? "combine2" : CSm == 3 ? "combine3" : "combine4", GS, KS, XW, NRT);
   const int nblk = a.K / 64;
   const int nu = (nblk + KS - 1) / KS;
   dim3 grid((a.N + fw - 1) / fw, (a.R + 8 * NRT - 1) / (8 * NRT)), block(WAVES * 64);
@@ -1377,6 +1382,7 @@ bool rows48_applies(const whk::GemvArgs& a) {
 }
 
 hipError_t launch_rows48(const whk::GemvArgs& a, hipStream_t stream) {
+  whk::g_form = "rows48";
   const size_t lds = (size_t)48 * a.K * 2 > 49152 ? (size_t)48 * a.K * 2 : 49152;     // x tile, later the partial sums
   static whk::LdsAttr attr2;
   { hipError_t e = whk::raise_dynamic_lds(attr2, (const void*)gemv_rows48_kernel<2>, 160 * 1024); if (e != hipSuccess) return e; }
@@ -1509,6 +1515,7 @@ bool rows48_stream_applies(const whk::GemvArgs& a) {
 }
 
 hipError_t launch_rows48_stream(const whk::GemvArgs& a, hipStream_t stream) {
+  whk::g_form = "rows48_stream";
   const size_t lds = (size_t)48 * a.K * 2 + (size_t)2 * a.K * 4;
   static whk::LdsAttr attr;
   { hipError_t e = whk::raise_dynamic_lds(attr, (const void*)gemv_rows48_stream_kernel, 160 * 1024); if (e != hipSuccess) return e; }
@@ -1565,6 +1572,8 @@ __global__ __launch_bounds__(256) void merge_partials_kernel(const T* __restrict
 
 namespace whk {
 
+thread_local const char* g_form = "";
+
 hipError_t launch_gemv(const GemvArgs& a, int dtype, hipStream_t stream) {
   if (a.R <= 0) return hipErrorInvalidValue;
   if (a.x_frag || a.y_frag) {
@@ -1619,6 +1628,7 @@ hipError_t launch_merge_partials(const void* part_o, const float* part_ml, int s
   if (splits < 1 || splits > DEC_ATTN_MAX_SPLITS || R <= 0 || H <= 0) return hipErrorInvalidValue;
   const int n = R * H * 16;
   const dim3 grid((n + 255) / 256), block(256);
+  g_form = dtype == 1 ? (splits <= 4 ? "merge<half,4>" : "merge<half,16>") : (splits <= 4 ? "merge<float,4>" : "merge<float,16>");
   if (dtype == 1) {
     if (splits <= 4)
       hipLaunchKernelGGL((merge_partials_kernel<half_t, 4>), grid, block, 0, stream, (const half_t*)part_o, part_ml, splits, R, H, (half_t*)out, o_ld, o_frag);

@@ -30,7 +30,18 @@
 #endif
 
 #include <atomic>
+#include <stdio.h>
+#include <string>
 namespace whk {
+
+// Form tag: every terminal dispatch branch of launch_gemv, launch_attn_decode, launch_gemm and launch_merge_partials stores
+// a stable name of the kernel form it picked ("gemv8/LN/gs3/ks2/xw8/rt3", "rt<half,8>/pro<8,0,16,4>", "attn/group_diag").
+// Host only, one store per host call, nothing on the device and no extra launch; decode steps replay from a graph, so the
+// store costs nothing there.  Read by the kernel test library (ktest.cpp: wht_last_form) to prove every form is reached.
+extern thread_local const char* g_form;
+// a name built once per template instantiation (the pointer stays valid for the life of the process)
+#define WH_FORM_NAME(...) ([&] { static const std::string s_ = [&] { char b_[96]; snprintf(b_, sizeof b_, __VA_ARGS__); \
+                                                                     return std::string(b_); }(); return s_.c_str(); }())
 
 // Dynamic LDS above 64 KB is a per-DEVICE function attribute (hipFuncSetAttribute): raise it once on every device this
 // process launches `fn` on.  `c` is the call site's own cache (function-local static).

@@ -1,0 +1,97 @@
+// ktest.cpp — test-only C entry points over the shipped kernel launchers (libwhisper_hip_ktest.so).
+// Linked from the same build/*.o objects as libwhisper_hip.so (Makefile), so tests/test_kernel_parity_gpu.py checks the
+// bytes that ship.  Arguments are flat (pointers, ints, strides): every wrapper fills the launcher's struct itself, so
+// the Python side mirrors no struct layout.  Each wrapper returns the launcher's hipError_t unchanged.
+#include <string.h>
+
+#include "kernels.h"
+
+using namespace whk;
+
+extern "C" {
+
+// name of the kernel form the last launch_gemv / launch_attn_decode / launch_gemm / launch_merge_partials on this thread picked
+const char* wht_last_form() { return g_form; }
+void wht_clear_form() { g_form = ""; }
+int wht_attn_decode_capacity(int dtype) { return attn_decode_capacity(dtype); }
+int wht_gemv8_will_run(int R, int N, int K, int pro) { return gemv8_will_run(R, N, K, pro) ? 1 : 0; }
+
+int wht_gemv(int dtype, int pro, const void* x, int64_t x_ld, const float* xf, int64_t xf_ld, const float* ln_w,
+             const float* ln_b, int ln_folded, const void* part_o, const float* part_ml, int splits, int H, const void* W,
+             const float* bias, int N, int K, int R, int x_frag, int y_frag, int epi, void* y, int64_t y_ld, float* resid,
+             int64_t resid_ld, void* kcache, void* vcache, int64_t cache_bs, const int* d_pos, int D, const int* lag,
+             int* bump, int bump_by, int* bump2, void* stream) {
+  GemvArgs a;
+  memset(&a, 0, sizeof a);
+  a.pro = pro; a.x = x; a.x_ld = x_ld; a.xf = xf; a.xf_ld = xf_ld; a.ln_w = ln_w; a.ln_b = ln_b; a.ln_folded = ln_folded;
+  a.part_o = part_o; a.part_ml = part_ml; a.splits = splits; a.H = H;
+  a.W = W; a.bias = bias; a.N = N; a.K = K; a.R = R; a.x_frag = x_frag; a.y_frag = y_frag;
+  a.epi = epi; a.y = y; a.y_ld = y_ld; a.resid = resid; a.resid_ld = resid_ld;
+  a.kcache = kcache; a.vcache = vcache; a.cache_bs = cache_bs; a.d_pos = d_pos; a.D = D; a.lag = lag;
+  a.bump = bump; a.bump_by = bump_by; a.bump2 = bump2;
+  return launch_gemv(a, dtype, (hipStream_t)stream);
+}
+
+int wht_merge_partials(const void* part_o, const float* part_ml, int splits, int R, int H, void* out, int64_t o_ld,
+                       int dtype, int o_frag, void* stream) {
+  return launch_merge_partials(part_o, part_ml, splits, R, H, out, o_ld, dtype, (hipStream_t)stream, o_frag);
+}
+
+int wht_attn_decode(int dtype, const void* q, int64_t q_ld, const void* k, int64_t k_ld, int64_t k_bs, const void* v,
+                    int64_t v_ld, int64_t v_bs, int64_t kv_hs, int H, int R, int kv_group, int Tk, const int* d_len,
+                    int len_plus, const int* lag, int splits, void* out, int64_t o_ld, int o_frag, void* part_o,
+                    float* part_ml, int* merge_cnt, const void* vt, int64_t vt_ld, int64_t vt_bs, void* stream) {
+  DecAttnArgs a;
+  memset(&a, 0, sizeof a);
+  a.q = q; a.q_ld = q_ld; a.k = k; a.k_ld = k_ld; a.k_bs = k_bs; a.v = v; a.v_ld = v_ld; a.v_bs = v_bs; a.kv_hs = kv_hs;
+  a.H = H; a.R = R; a.kv_group = kv_group; a.Tk = Tk; a.d_len = d_len; a.len_plus = len_plus; a.lag = lag;
+  a.splits = splits; a.out = out; a.o_ld = o_ld; a.o_frag = o_frag; a.part_o = part_o; a.part_ml = part_ml;
+  a.merge_cnt = merge_cnt; a.vt = vt; a.vt_ld = vt_ld; a.vt_bs = vt_bs;
+  return launch_attn_decode(a, dtype, (hipStream_t)stream);
+}
+
+int wht_gemm(int dtype, int out_f32, int batch, const void* A, int64_t lda, int64_t a_bs, const void* W, int64_t ldw,
+             int64_t w_bs, void* C, int64_t ldc, int64_t c_bs, const float* bias, int bias_on_m, const float* res,
+             int64_t ldr, int64_t r_bs, int res_mod, int act, int M, int N, int K, void* stream) {
+  GemmArgs a;
+  memset(&a, 0, sizeof a);
+  a.A = A; a.lda = lda; a.a_bs = a_bs; a.W = W; a.ldw = ldw; a.w_bs = w_bs; a.C = C; a.ldc = ldc; a.c_bs = c_bs;
+  a.bias = bias; a.bias_on_m = bias_on_m; a.res = res; a.ldr = ldr; a.r_bs = r_bs; a.res_mod = res_mod; a.act = act;
+  a.M = M; a.N = N; a.K = K;
+  return launch_gemm(a, dtype, out_f32, batch, (hipStream_t)stream);
+}
+
+int wht_attn_flash_f16(const void* q, int64_t q_ld, int64_t q_bs, const void* k, int64_t k_ld, int64_t k_bs,
+                       const void* vt, int64_t vt_ld, int64_t vt_bs, void* out, int64_t o_ld, int64_t o_bs, int B, int H,
+                       int T, int prescaled, int Tq, void* stream) {
+  return launch_attn_flash_f16(q, q_ld, q_bs, k, k_ld, k_bs, vt, vt_ld, vt_bs, out, o_ld, o_bs, B, H, T, prescaled,
+                               (hipStream_t)stream, Tq);
+}
+
+int wht_layernorm(const float* x, int64_t ldx, const float* w, const float* b, void* out, int64_t ldo, int64_t rows, int D,
+                  int dtype, void* stream) {
+  return launch_layernorm(x, ldx, w, b, out, ldo, rows, D, dtype, (hipStream_t)stream);
+}
+
+int wht_scatter_kv(const void* qkv, int R, int T0, int D, const int* d_offset, int n_ctx, void* kcache, void* vcache,
+                   int dtype, void* stream) {
+  return launch_scatter_kv(qkv, R, T0, D, d_offset, n_ctx, kcache, vcache, dtype, (hipStream_t)stream);
+}
+
+int wht_gather_cache(const void* src, void* dst, const int* src_idx, int R, int64_t row_bytes, int64_t used_bytes,
+                     void* stream) {
+  return launch_gather_cache(src, dst, src_idx, R, row_bytes, used_bytes, (hipStream_t)stream);
+}
+
+int wht_permute_groups(void* k_base, void* v_base, int n_layers, int64_t layer_bytes, int n_audio, int G, int64_t row_bytes,
+                       int64_t used_bytes, const int* src_idx, const int* copy_from, int64_t pos_bytes, void* stream) {
+  return launch_permute_groups(k_base, v_base, n_layers, layer_bytes, n_audio, G, row_bytes, used_bytes, src_idx, copy_from,
+                               pos_bytes, (hipStream_t)stream);
+}
+
+int wht_replicate_row(void* base, int64_t layer_bytes, int n_layers, int64_t row_bytes, int src_row, int dst_row0, int G,
+                      int64_t used_bytes, void* stream) {
+  return launch_replicate_row(base, layer_bytes, n_layers, row_bytes, src_row, dst_row0, G, used_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"
