@@ -360,6 +360,24 @@ int wh_task_align_batch(wh_task *t, const int32_t *layers, const int32_t *heads,
                         const int32_t *n_frames, int width, int row_begin, float qk_scale, float *cost_out,
                         int8_t *trace_out, int64_t trace_stride, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- cutting one long recording at pauses (no counterpart in the reference) ---------------- */
+/* Level of every frame of a log-mel spectrogram as wh_log_mel writes it (values (x + 4) / 4, x = log10 mel power):
+ *   L[f] = log10( (1 / n_mels) * sum_m 10^(4 * mel[m][f] - 4) ),  0 <= f < content_frames  (log10 of the mean mel power).
+ * mel: fp32 [n_mels][frame_stride] (frame_stride >= content_frames), level_out: fp32 [content_frames]. */
+int wh_frame_level(const float *mel, int n_mels, int64_t frame_stride, int64_t content_frames,
+                   float *level_out, void *stream);
+/* Cut cost and cut walk on a given level (device fp32 [content_frames]):
+ *   C[f] = max L[g] over max(0, f - guard_frames) <= g <= min(content_frames - 1, f + guard_frames);
+ *   a = 0; while content_frames - a > max_frames: c = the f in [a + min_frames, a + max_frames] with the smallest C[f],
+ *   the largest such f among equal minima; emit c; a = c.
+ * The chunks [0, c0), [c0, c1), ..., [c_last, content_frames) have at most max_frames frames, all but the last at least
+ * min_frames.  Given the level, C and the cuts are exact (a sliding max and comparisons).
+ * cuts_out: int32 [max_cuts] (device), n_cuts_out: int32 [1] (device); cost_out may be NULL, else fp32 [content_frames].
+ * Status 1 on null / out-of-range arguments (guard_frames > 64, min_frames < 1, min_frames > max_frames, max_cuts <
+ * content_frames / min_frames), before any device work.  Stream-ordered: the call does not wait for the device. */
+int wh_speech_cuts(const float *level, int64_t content_frames, int min_frames, int max_frames, int guard_frames,
+                   float *cost_out, int32_t *cuts_out, int32_t *n_cuts_out, int max_cuts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1692,3 +1692,31 @@ extern "C" int wh_align_matrix(const float* qk, int n_heads, int n_tok, int n_au
                              (float*)scratch, (hipStream_t)stream));
   return WH_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// cutting one long file at pauses (chunk.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int wh_frame_level(const float* mel, int n_mels, int64_t frame_stride, int64_t content_frames, float* level_out,
+                              void* stream) {
+  if (!mel || !level_out || n_mels <= 0 || content_frames <= 0 || frame_stride < content_frames) return WH_ERR_ARG;
+  HIPCHK(launch_frame_level(mel, n_mels, frame_stride, content_frames, level_out, (hipStream_t)stream));
+  return WH_OK;
+}
+
+extern "C" int wh_speech_cuts(const float* level, int64_t content_frames, int min_frames, int max_frames, int guard_frames,
+                              float* cost_out, int32_t* cuts_out, int32_t* n_cuts_out, int max_cuts, void* stream) {
+  if (!level || !cuts_out || !n_cuts_out || content_frames <= 0 || content_frames > INT32_MAX) return WH_ERR_ARG;
+  if (guard_frames < 0 || guard_frames > 64 || min_frames < 1 || min_frames > max_frames) return WH_ERR_ARG;
+  if (max_cuts < 1 || max_cuts < content_frames / min_frames) return WH_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  float* cost = cost_out;
+  if (!cost) HIPCHK(hipMallocAsync((void**)&cost, (size_t)content_frames * sizeof(float), s));   // stream-ordered: no host wait
+  hipError_t e = launch_speech_cuts(level, (int)content_frames, min_frames, max_frames, guard_frames, cost, cuts_out,
+                                    n_cuts_out, max_cuts, s);
+  if (!cost_out) {
+    hipError_t f = hipFreeAsync(cost, s);
+    if (e == hipSuccess) e = f;
+  }
+  HIPCHK(e);
+  return WH_OK;
+}

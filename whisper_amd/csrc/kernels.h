@@ -345,4 +345,13 @@ hipError_t launch_dtw_backtrace_batch(const int8_t* trace, int64_t trace_bs, con
 hipError_t launch_align_matrix(const float* qk, int H, int T, int Tk, int F, int width, int row_begin,
                                int row_end, float qk_scale, float* out, float* scratch, hipStream_t stream);
 
+// ---- chunk.hip -----------------------------------------------------------------------------
+// L[f] = log10 of the mean mel power of frame f (definitions at the top of chunk.hip); mel fp32 [n_mels][frame_stride]
+hipError_t launch_frame_level(const float* mel, int n_mels, int64_t frame_stride, int64_t content, float* level,
+                              hipStream_t stream);
+// cost[f] = max of level over [f - guard, f + guard] (guard <= 64), then the cut walk by one workgroup: cuts [max_cuts],
+// n_cuts [1] (device)
+hipError_t launch_speech_cuts(const float* level, int content, int min_frames, int max_frames, int guard, float* cost,
+                              int* cuts, int* n_cuts, int max_cuts, hipStream_t stream);
+
 }  // namespace whk

@@ -126,6 +126,9 @@ SIGNATURES = {
                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "wh_align_matrix": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "wh_frame_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "wh_speech_cuts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int, C.c_void_p]),
 }
 
 
@@ -989,3 +992,33 @@ def align_matrix(qk: torch.Tensor, n_frames: int, width: int, row_begin: int, ro
     check(lib().wh_align_matrix(q.data_ptr(), H, T, Tk, n_frames, width, row_begin, row_end, float(qk_scale),
                                 out.data_ptr(), scratch.data_ptr(), stream_ptr(s)), "wh_align_matrix")
     return out
+
+
+def frame_level(mel: torch.Tensor, content_frames: int) -> torch.Tensor:
+    """mel fp32 [n_mels][n_frames] on the GPU as log_mel_spectrogram leaves it -> level fp32 [content_frames]:
+    log10 of the mean mel power of every frame (include/whisper_hip.h, wh_frame_level)."""
+    require_gpu(mel.device)
+    assert mel.dim() == 2 and 0 < content_frames <= mel.shape[1]
+    m = mel.contiguous().float()
+    out = torch.empty(content_frames, dtype=torch.float32, device=m.device)
+    s = torch.cuda.current_stream(m.device)
+    check(lib().wh_frame_level(m.data_ptr(), m.shape[0], m.shape[1], content_frames, out.data_ptr(), stream_ptr(s)),
+          "wh_frame_level")
+    return out
+
+
+def speech_cuts(level: torch.Tensor, min_frames: int = 1500, max_frames: int = 3000, guard_frames: int = 10):
+    """level fp32 [content_frames] on the GPU (frame_level) -> (cuts: list[int], cost: fp32 [content_frames] on the GPU): the
+    cut cost (sliding max of the level over +-guard_frames) and the frames at which the cut walk of wh_speech_cuts splits
+    the file.  The three kernels are stream-ordered; the only host wait is the download of the cuts at the end."""
+    require_gpu(level.device)
+    lv = level.contiguous().float()
+    n = lv.numel()
+    max_cuts = max(1, n // max(1, min_frames))
+    cost = torch.empty_like(lv)
+    cuts = torch.empty(max_cuts, dtype=torch.int32, device=lv.device)
+    count = torch.empty(1, dtype=torch.int32, device=lv.device)
+    s = torch.cuda.current_stream(lv.device)
+    check(lib().wh_speech_cuts(lv.data_ptr(), n, min_frames, max_frames, guard_frames, cost.data_ptr(), cuts.data_ptr(),
+                               count.data_ptr(), max_cuts, stream_ptr(s)), "wh_speech_cuts")
+    return cuts[: int(count.item())].tolist(), cost

@@ -30,6 +30,7 @@ from .decoding import decode as decode_function
 from .decoding import detect_language as detect_language_function
 from .transcribe import transcribe as transcribe_function
 from .transcribe import transcribe_batch as transcribe_batch_function
+from .transcribe import transcribe_chunked as transcribe_chunked_function
 
 
 @dataclass
@@ -383,4 +384,5 @@ class Whisper:
     detect_language = detect_language_function
     transcribe = transcribe_function
     transcribe_batch = transcribe_batch_function     # extension: lock-step batching over files
+    transcribe_chunked = transcribe_chunked_function   # extension: one long file cut at pauses, chunks decoded batched
     decode = decode_function

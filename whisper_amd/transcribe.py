@@ -126,9 +126,9 @@ class _Transcriber:
             kwargs.pop("best_of", None)        # greedy / beam: no best-of
         return DecodingOptions(**kwargs, temperature=t)
 
-    def run(self, audio) -> dict:
+    def run(self, audio, mel: Optional[torch.Tensor] = None) -> dict:
         """one file, windows decoded one at a time (the reference's control flow)"""
-        walk = self._walk(audio)
+        walk = self._walk(audio, mel)
         try:
             request = next(walk)
             while True:
@@ -400,6 +400,15 @@ def transcribe(
     ).run(audio)
 
 
+# transcribe()'s keyword arguments that belong to the walk, in the order _Transcriber takes them, with their defaults; the
+# rest of a caller's keywords are DecodingOptions fields
+_WALK_DEFAULTS = dict(verbose=None, temperature=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0), compression_ratio_threshold=2.4,
+                      logprob_threshold=-1.0, no_speech_threshold=0.6, condition_on_previous_text=True,
+                      initial_prompt=None, carry_initial_prompt=False, word_timestamps=False,
+                      prepend_punctuations="\"'“¿([{-", append_punctuations="\"'.。,，!！?？:：”)]}、",
+                      clip_timestamps="0", hallucination_silence_threshold=None)
+
+
 def _options_key(opts: dict):
     """hashable identity of a DecodingOptions kwargs dict without its prompt: windows may share one batched decode
     only if every other option is the same (the prompts go to DecodingTask as one token list per row)"""
@@ -456,7 +465,8 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
     share a call in every device-side mode — greedy, sampling and beam search with the stock decoder and filters; the
     beams of a segment share its prompt.  With ragged rows the beam loop copies whole cache rows when beams are
     reordered instead of only the part after the shared history).  Results are the same dicts `transcribe`
-    returns, in input order.  Windows of one file stay sequential (seek and prompt depend on the previous window).
+    returns, in input order.  Windows of one file stay sequential (seek and prompt depend on the previous window; for ONE
+    long file see `transcribe_chunked`).
     Windows whose result trips the temperature-fallback criteria climb the temperature ladder together: the next
     rung decodes them as a batch again (sampling runs on the device, `best_of` rows per window).  With
     `word_timestamps` the alignments of the windows just decoded are computed together (find_alignment_batch).
@@ -490,15 +500,7 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
             for i, r in zip(ids, part):
                 merged[i] = r
         return merged
-    names = ("verbose", "temperature", "compression_ratio_threshold", "logprob_threshold", "no_speech_threshold",
-             "condition_on_previous_text", "initial_prompt", "carry_initial_prompt", "word_timestamps",
-             "prepend_punctuations", "append_punctuations", "clip_timestamps", "hallucination_silence_threshold")
-    defaults = dict(verbose=None, temperature=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0), compression_ratio_threshold=2.4,
-                    logprob_threshold=-1.0, no_speech_threshold=0.6, condition_on_previous_text=True,
-                    initial_prompt=None, carry_initial_prompt=False, word_timestamps=False,
-                    prepend_punctuations="\"'“¿([{-", append_punctuations="\"'.。,，!！?？:：”)]}、",
-                    clip_timestamps="0", hallucination_silence_threshold=None)
-    fixed = {k: kwargs.pop(k, defaults[k]) for k in names}
+    fixed = {k: kwargs.pop(k, default) for k, default in _WALK_DEFAULTS.items()}
     audios = list(audios)
     if batch_size < 1:
         raise ValueError(f"batch_size must be at least 1 (got {batch_size})")
@@ -506,29 +508,12 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
         max_active_files = 2 * batch_size
     if max_active_files < 1:
         raise ValueError(f"max_active_files must be at least 1 (got {max_active_files})")
-    workers = [_Transcriber(model, *[fixed[k] for k in names], dict(kwargs)) for _ in audios]
+    workers = [_Transcriber(model, *fixed.values(), dict(kwargs)) for _ in audios]
     detect = kwargs.get("language") is None and model.is_multilingual and len(audios) > 1
-    walks: List[Optional[object]] = [None] * len(audios)
-    results: List[Optional[dict]] = [None] * len(audios)
-    pending = {}
-    waiting = list(range(len(audios)))          # files not started yet: neither decoded nor on the device
 
-    def advance(i: int, value):
-        try:
-            pending[i] = walks[i].send(value) if value is not None else next(walks[i])
-        except StopIteration as stop:
-            pending.pop(i, None)
-            walks[i] = None                      # drops the file's whole-file mel
-            results[i] = stop.value
-
-    def admit():
-        """start state machines until `max_active_files` are running: only those files are decoded to PCM and hold a
-        whole-file spectrogram on the device, so memory follows the window, not the total audio duration"""
-        room = max_active_files - len(pending)
-        if room <= 0 or not waiting:
-            return
-        take = waiting[:room]
-        del waiting[:room]
+    def start(take: List[int]) -> list:
+        """only the files admitted are decoded to PCM and hold a whole-file spectrogram on the device, so memory follows the
+        window of active files, not the total audio duration"""
         loaded = _load_all([audios[i] for i in take])
         mels = [None] * len(take)
         if detect:
@@ -543,8 +528,39 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
                     workers[i].decode_options["language"] = max(p, key=p.get)
                     if fixed["verbose"] is not None:
                         print(f"Detected language: {LANGUAGES[workers[i].decode_options['language']].title()}")
-        for i, a, m in zip(take, loaded, mels):
-            walks[i] = workers[i]._walk(a, m)
+        return [workers[i]._walk(a, m) for i, a, m in zip(take, loaded, mels)]
+
+    return _drive_lockstep(model, workers, start, batch_size, max_active_files)
+
+
+def _drive_lockstep(model: "Whisper", workers: List[_Transcriber], start, batch_size: int, max_active: int) -> List[dict]:
+    """The lock-step driver of `transcribe_batch` and `transcribe_chunked`: advances the state machines (`_walk` generators)
+    of `workers` together and answers what they yield — the windows pending at the same moment as batched decodes of up to
+    `batch_size` rows, taken up the temperature ladder together, and their word-alignment requests as find_alignment_batch
+    passes.  At most `max_active` machines run at once; `start(ids)` returns the generators of workers `ids` when they are
+    admitted.  Returns every worker's result dict, in order."""
+    walks: List[Optional[object]] = [None] * len(workers)
+    results: List[Optional[dict]] = [None] * len(workers)
+    pending = {}
+    waiting = list(range(len(workers)))         # not started yet
+
+    def advance(i: int, value):
+        try:
+            pending[i] = walks[i].send(value) if value is not None else next(walks[i])
+        except StopIteration as stop:
+            pending.pop(i, None)
+            walks[i] = None                      # drops the file's whole-file mel
+            results[i] = stop.value
+
+    def admit():
+        """start state machines until `max_active` are running"""
+        room = max_active - len(pending)
+        if room <= 0 or not waiting:
+            return
+        take = waiting[:room]
+        del waiting[:room]
+        for i, walk in zip(take, start(take)):
+            walks[i] = walk
             advance(i, None)
 
     admit()
@@ -614,3 +630,90 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
             advance(i, result)
         admit()
     return results
+
+
+def _check_chunk_arguments(min_chunk_s: float, guard_s: float) -> None:
+    if not 0.0 < min_chunk_s <= N_FRAMES / FRAMES_PER_SECOND:
+        raise ValueError(f"min_chunk_s must lie in (0, 30] (got {min_chunk_s})")
+    if not 0.0 <= guard_s <= 0.64:
+        raise ValueError(f"guard_s must lie in [0, 0.64] (got {guard_s})")
+
+
+def plan_chunks(mel: torch.Tensor, content_frames: int, min_chunk_s: float = 15.0, guard_s: float = 0.1) -> List[Tuple[int, int]]:
+    """Where `transcribe_chunked` cuts a file: `[(start_frame, end_frame), ...]` covering `[0, content_frames)` of the
+    whole-file log-mel spectrogram `mel` (fp32 `[n_mels][n_frames]` on the GPU, as `log_mel_spectrogram` leaves it).
+    Computed on the device (csrc/chunk.hip): the level of a frame is log10 of its mean mel power, the cost
+    of cutting at a frame is the highest level within `guard_s` of it, and from the start of every chunk the next cut is
+    the cheapest frame between `min_chunk_s` and 30 s further on (the last such frame among equally cheap ones).  Every
+    chunk has at most 3000 frames, every chunk but the last at least `min_chunk_s`; a file of at most 30 s is one chunk
+    and launches nothing; an empty file has no chunk."""
+    _check_chunk_arguments(min_chunk_s, guard_s)
+    content_frames = int(content_frames)
+    if content_frames <= 0:
+        return []
+    if content_frames <= N_FRAMES:
+        return [(0, content_frames)]
+    from . import hip
+    cuts, _ = hip.speech_cuts(hip.frame_level(mel, content_frames), max(1, round(min_chunk_s * FRAMES_PER_SECOND)), N_FRAMES,
+                              round(guard_s * FRAMES_PER_SECOND))
+    bounds = [0] + cuts + [content_frames]
+    return list(zip(bounds[:-1], bounds[1:]))
+
+
+def transcribe_chunked(model: "Whisper", audio: Union[str, np.ndarray, torch.Tensor], *, batch_size: int = 24,
+                       min_chunk_s: float = 15.0, guard_s: float = 0.1, **kwargs) -> dict:
+    """Transcribe ONE long recording with a wide decode chain (no counterpart in the reference, whose windows are strictly
+    sequential: every window's seek and prompt depend on the tokens of the one before, so `transcribe` decodes an hour of
+    audio as a 1-row chain).  The file is cut at pauses into chunks of `min_chunk_s` to 30 s (`plan_chunks`: chosen on the
+    device from the whole-file spectrogram, which is computed once and shared by all chunks), every chunk is an ordinary
+    `transcribe` walk restricted to its range (`clip_timestamps=[start, end]`, absolute times in its segments), and the
+    walks are driven in lock-step by the driver of `transcribe_batch`: the windows pending together are decoded as batches
+    of up to `batch_size` rows.  `audio` and the keyword arguments are those of `transcribe`.
+
+    What follows from cutting:
+      * the previous-text prompt (`condition_on_previous_text`) carries WITHIN a chunk — a chunk takes more than one window
+        when the decoder's timestamps stop early — and never across chunks; `initial_prompt` conditions the start of
+        every chunk;
+      * the language is detected once, on the first 30 s of the file, as `transcribe` does;
+      * the temperature ladder, `word_timestamps`, `hallucination_silence_threshold` and the thresholds work as in
+        `transcribe`, because the walk is the same code; a silent chunk is left to the walk's no-speech rule;
+      * `clip_timestamps` cannot be combined with chunking (ValueError), nor can `min_chunk_s` outside (0, 30] or `guard_s`
+        above 0.64 (the cut kernel's halo);
+      * `verbose=True` prints the segments chunk by chunk in completion order, not in file order; there is no progress bar.
+
+    Returns the dict `transcribe` returns — `segments` concatenated in chunk order with `id` renumbered, `text` the
+    concatenation of the chunks' texts, `language` — plus `chunks`: `[(start_s, end_s), ...]`.  A file of at most 30 s has no
+    cut: the result is exactly that of `transcribe` (with its one chunk listed); an empty file gives the empty result."""
+    if "clip_timestamps" in kwargs:
+        raise ValueError("transcribe_chunked chooses the ranges itself: clip_timestamps cannot be combined with it")
+    _check_chunk_arguments(min_chunk_s, guard_s)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be at least 1 (got {batch_size})")
+    fixed = {k: kwargs.pop(k, default) for k, default in _WALK_DEFAULTS.items()}
+    mel = log_mel_spectrogram(audio, model.dims.n_mels, padding=N_SAMPLES, device=model.device)
+    plan = plan_chunks(mel, mel.shape[-1] - N_FRAMES, min_chunk_s, guard_s)
+    chunks = [(a / FRAMES_PER_SECOND, b / FRAMES_PER_SECOND) for a, b in plan]
+    if len(plan) <= 1:
+        result = _Transcriber(model, *fixed.values(), dict(kwargs)).run(audio, mel)
+        return dict(result, chunks=chunks)
+
+    if kwargs.get("language") is None and model.is_multilingual:
+        # once, on the head of the file, before the chunks' state machines start (each would detect it on the same head)
+        dtype = torch.float16 if kwargs.get("fp16", True) and model.device != torch.device("cpu") else torch.float32
+        if fixed["verbose"]:
+            print("Detecting language using up to the first 30 seconds. Use `--language` to specify the language")
+        _, probs = model.detect_language(pad_or_trim(mel, N_FRAMES).to(model.device).to(dtype))
+        kwargs["language"] = max(probs, key=probs.get)
+        if fixed["verbose"] is not None:
+            print(f"Detected language: {LANGUAGES[kwargs['language']].title()}")
+    if fixed["verbose"] is False:
+        fixed["verbose"] = None                  # no progress bar per chunk
+    workers = []
+    for start_s, end_s in chunks:                # frame / 100.0: round(ts * FRAMES_PER_SECOND) maps it back exactly
+        workers.append(_Transcriber(model, *{**fixed, "clip_timestamps": [start_s, end_s]}.values(), dict(kwargs)))
+    parts = _drive_lockstep(model, workers, lambda take: [workers[i]._walk(None, mel) for i in take], batch_size,
+                            len(workers))
+    segments = [segment for part in parts for segment in part["segments"]]
+    return dict(text="".join(part["text"] for part in parts),
+                segments=[{**segment, "id": i} for i, segment in enumerate(segments)],
+                language=parts[0]["language"], chunks=chunks)
