@@ -140,6 +140,34 @@ const char *wh_last_hip_error_string(void);
 int wh_log_mel(const float *audio, int64_t n_samples, int batch, int n_mels, const float *filters,
                float *out, void *scratch, void *stream);
 
+/* ---- audio front end: device-side ingest (load_audio's down-mix + resampling + 16-bit quantisation; no counterpart in
+ * the reference, which leaves all three to ffmpeg, whisper/audio.py:25-62) ------------------------------------------- */
+/* sample formats of the interleaved PCM a WAV / FLAC reader holds */
+enum {
+  WH_PCM_U8 = 0,         /* 8-bit WAV: offset binary, value = byte - 128, full scale 128; bits must be 8 */
+  WH_PCM_S16 = 1,        /* int16, full scale 2^(bits-1), 1 <= bits <= 16 */
+  WH_PCM_S32 = 2,        /* int32, full scale 2^(bits-1), 1 <= bits <= 32: FLAC decoder output, 24-bit WAV sign-extended, 32-bit WAV */
+  WH_PCM_F32 = 3,        /* float, full scale 1 (bits ignored) */
+  WH_PCM_F64 = 4         /* double, full scale 1 (bits ignored) */
+};
+/* longest filter the call accepts, in taps (64 MB of float64) */
+#define WH_RESAMPLE_MAX_TAPS (1 << 23)
+/* pcm: device, [n_frames][channels] interleaved, 1 <= channels <= 8.  taps: device float64 [2 * half_len + 1], centre at
+ * index half_len.  up / down: the rate ratio in lowest terms.  out: device fp32 [n_out], n_out = ceil(n_frames * up / down).
+ *   mono[k] = (sum over channels of pcm[k][c]) / (channels * full_scale), zero outside [0, n_frames)
+ *   y[m]    = sum over k with |m * down - k * up| <= half_len of taps[m * down - k * up + half_len] * mono[k]
+ *   out[m]  = clip(rint(32768 * y[m]), -32768, 32767) / 32768        (rint: round half to even)
+ * evaluated in float64.  With the taps of whisper_amd.audio.resample_taps this is scipy.signal.resample_poly(mono, up, down)
+ * followed by the 16-bit quantisation of ffmpeg's s16le output; up == down == 1 with the single tap 1.0 (half_len 0) is
+ * down-mix + quantisation only.
+ * Status 1 (before any device work) on null pointers, channels outside 1 - 8, up or down < 1 or not coprime, a wrong n_out, an
+ * unknown format or bits outside the format's range, half_len < 0, and on sizes whose 64-bit index products could overflow:
+ * n_frames < 0 or > 2^38 (3 days at 1 MHz), up or down > 2^24; WH_ERR_LIMIT when 2 * half_len + 1 > WH_RESAMPLE_MAX_TAPS or down / up is
+ * so large that one output's input span exceeds a workgroup's LDS (about 200: no audio rate comes near it) — callers fall
+ * back to a host resampler.  n_frames == 0 succeeds and writes nothing.  Stream-ordered: the call does not wait. */
+int wh_resample(const void *pcm, int sample_format, int bits, int channels, int64_t n_frames, const double *taps,
+                int up, int down, int half_len, float *out, int64_t n_out, void *stream);
+
 /* ---- model handle -------------------------------------------------------------------------- */
 /* Stands in for Whisper.__init__ + load_state_dict (whisper/__init__.py:154-156): the caller has
  * already packed the checkpoint into device memory; this only records dims and pointers. */

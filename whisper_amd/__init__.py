@@ -19,7 +19,9 @@ from typing import List, Optional, Union
 
 import torch
 
-from .audio import load_audio, log_mel_spectrogram, pad_or_trim
+from . import audio as _audio
+from .audio import SAMPLE_RATE as _SAMPLE_RATE
+from .audio import log_mel_spectrogram, pad_or_trim
 from .decoding import (DecodingOptions, DecodingResult, decode, decode_many, detect_language, run_in_lanes,
                        run_interleaved)
 from .model import ModelDimensions, Whisper
@@ -29,6 +31,14 @@ from .transcribe import plan_chunks, transcribe, transcribe_batch, transcribe_ch
 from . import launcher  # noqa: E402,F401  (multi-GPU layer: broadcast_weights, transcribe_sharded)
 
 __version__ = "0.1.0"
+
+
+def load_audio(file: str, sr: int = _SAMPLE_RATE):
+    """The reference's `whisper.load_audio`, parameter for parameter (whisper/audio.py:25; the package-level names keep the
+    reference's parameter lists): `file` decoded to mono float32 at `sr` Hz on the host.  `whisper_amd.audio.load_audio`
+    is the same function with one more keyword, `device`: the samples as a tensor on that GPU, WAV / FLAC down-mixed,
+    resampled and quantised there."""
+    return _audio.load_audio(file, sr)
 
 
 def _fetch(url: str, root: str, in_memory: bool) -> Union[bytes, str]:

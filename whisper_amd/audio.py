@@ -27,15 +27,18 @@ FRAMES_PER_SECOND = exact_div(SAMPLE_RATE, HOP_LENGTH)
 TOKENS_PER_SECOND = exact_div(SAMPLE_RATE, N_SAMPLES_PER_TOKEN)
 
 
-def _read_wav(path: str, sr: int) -> Optional[np.ndarray]:
-    """Minimal RIFF/WAVE reader (PCM 8/16/24/32-bit and float32) used when ffmpeg is not installed."""
+def _parse_wav(path: str):
+    """Minimal RIFF/WAVE reader (PCM 8/16/24/32-bit and float32/64): (samples [frames][channels] in their stored type — uint8,
+    int16, int32, float32, float64; 24-bit sign-extended to int32 —, sample rate, bits per sample), or None for a file it
+    cannot read.  The samples are a view of the file's bytes wherever the stored type allows it."""
     with open(path, "rb") as f:
-        data = f.read()
+        data = bytearray(os.fstat(f.fileno()).st_size)
+        data = memoryview(data)[: f.readinto(data)]
     if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
         return None
     pos, fmt, pcm = 12, None, None
     while pos + 8 <= len(data):
-        tag, size = data[pos: pos + 4], struct.unpack("<I", data[pos + 4: pos + 8])[0]
+        tag, size = bytes(data[pos: pos + 4]), struct.unpack("<I", data[pos + 4: pos + 8])[0]
         body = data[pos + 8: pos + 8 + size]
         if tag == b"fmt ":
             if len(body) < 16:
@@ -54,23 +57,59 @@ def _read_wav(path: str, sr: int) -> Optional[np.ndarray]:
     if channels == 0 or rate == 0:
         return None
     if code == 3 and bits == 32:
-        x = np.frombuffer(pcm[: len(pcm) // 4 * 4], "<f4").astype(np.float32)
+        x = np.frombuffer(pcm[: len(pcm) // 4 * 4], "<f4")
     elif code == 3 and bits == 64:
-        x = np.frombuffer(pcm[: len(pcm) // 8 * 8], "<f8").astype(np.float32)
+        x = np.frombuffer(pcm[: len(pcm) // 8 * 8], "<f8")
     elif code == 1 and bits == 16:
-        x = np.frombuffer(pcm[: len(pcm) // 2 * 2], "<i2").astype(np.float32) / 32768.0
+        x = np.frombuffer(pcm[: len(pcm) // 2 * 2], "<i2")
     elif code == 1 and bits == 32:
-        x = np.frombuffer(pcm[: len(pcm) // 4 * 4], "<i4").astype(np.float32) / 2147483648.0
+        x = np.frombuffer(pcm[: len(pcm) // 4 * 4], "<i4")
     elif code == 1 and bits == 24:
         b = np.frombuffer(pcm[: len(pcm) // 3 * 3], np.uint8).reshape(-1, 3).astype(np.int32)
         v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
-        x = (v - ((v & 0x800000) << 1)).astype(np.float32) / 8388608.0
+        x = v - ((v & 0x800000) << 1)
     elif code == 1 and bits == 8:
-        x = (np.frombuffer(pcm, np.uint8).astype(np.float32) - 128.0) / 128.0
+        x = np.frombuffer(pcm, np.uint8)
     else:
         return None
-    x = x[: len(x) // channels * channels].reshape(-1, channels)
-    return _to_mono_s16(x, rate, sr)
+    return x[: len(x) // channels * channels].reshape(-1, channels), rate, bits
+
+
+def _pcm_to_float(pcm: np.ndarray, bits: int) -> np.ndarray:
+    """stored samples (`_parse_wav`, `decode_flac`) -> float32 in [-1, 1): uint8 is offset binary, the signed integer types
+    have full scale 2^(bits-1)"""
+    if pcm.dtype == np.uint8:
+        return (pcm.astype(np.float32) - 128.0) / 128.0
+    if pcm.dtype.kind == "i":
+        return pcm.astype(np.float32) / float(1 << (bits - 1))
+    return pcm.astype(np.float32)
+
+
+def _read_wav(path: str, sr: int) -> Optional[np.ndarray]:
+    parsed = _parse_wav(path)
+    if parsed is None:
+        return None
+    pcm, rate, bits = parsed
+    return _to_mono_s16(_pcm_to_float(pcm, bits), rate, sr)
+
+
+@lru_cache(maxsize=None)
+def resample_taps(rate: int, sr: int) -> np.ndarray:
+    """The filter scipy.signal.resample_poly(x, up, down) designs by default for up / down = sr / rate in lowest terms, as
+    float64 [2 * half + 1] with half = 10 * max(up, down) (centre at index half): a Kaiser(5.0)-windowed sinc with cutoff
+    1 / max(up, down), unit gain at DC, times up.  [1.0] when rate == sr.  Read-only (the array is cached)."""
+    from math import gcd
+    g = gcd(int(rate), int(sr))
+    up, down = int(sr) // g, int(rate) // g
+    if up == down:
+        taps = np.ones(1, dtype=np.float64)
+    else:
+        m = max(up, down)
+        half = 10 * m
+        h = np.kaiser(2 * half + 1, 5.0) * np.sinc(np.arange(-half, half + 1, dtype=np.float64) / m) / m
+        taps = up * h / h.sum()
+    taps.setflags(write=False)
+    return taps
 
 
 def _to_mono_s16(x: np.ndarray, rate: int, sr: int) -> np.ndarray:
@@ -125,20 +164,92 @@ def decode_flac(data: bytes):
     return pcm, rate.value, bps.value
 
 
-def _read_flac(path: str, sr: int) -> Optional[np.ndarray]:
+def _parse_flac(path: str):
+    """(int32 samples [frames][channels], sample rate, bits per sample) of a FLAC file, None for any other file"""
     with open(path, "rb") as f:
         data = f.read()
     if data[:4] != b"fLaC" and data[:3] != b"ID3":
         return None
-    pcm, rate, bps = decode_flac(data)
-    return _to_mono_s16(pcm.astype(np.float32) / float(1 << (bps - 1)), rate, sr)
+    return decode_flac(data)
 
 
-def load_audio(file: str, sr: int = SAMPLE_RATE) -> np.ndarray:
+def _read_flac(path: str, sr: int) -> Optional[np.ndarray]:
+    parsed = _parse_flac(path)
+    if parsed is None:
+        return None
+    pcm, rate, bps = parsed
+    return _to_mono_s16(_pcm_to_float(pcm, bps), rate, sr)
+
+
+def _sniff(file: str) -> Optional[str]:
+    """"wav" / "flac" from the first bytes of `file` (a FLAC stream may follow an ID3v2 tag, which the native decoder skips),
+    None for any other container — or for something that is no readable file"""
+    try:
+        with open(file, "rb") as f:
+            head = f.read(12)
+            if head[:4] == b"RIFF" and head[8:12] == b"WAVE":
+                return "wav"
+            if head[:3] == b"ID3" and len(head) >= 10:
+                f.seek(10 + ((head[6] & 127) << 21 | (head[7] & 127) << 14 | (head[8] & 127) << 7 | (head[9] & 127)))
+                head = f.read(4)
+            return "flac" if head[:4] == b"fLaC" else None
+    except OSError:
+        return None
+
+
+MAX_DEVICE_CHANNELS = 8             # wh_resample: 1 - 8 channels
+
+
+def _ingest_host(file: str, sr: int):
+    """Host half of the device-side ingest (thread-safe; the FLAC decoder releases the GIL): the stored PCM of a WAV / FLAC
+    file as (pcm, rate, bits).  Everything the native route does not take — another container (an ID3-tagged MP3 included), a
+    WAV / FLAC the native readers refuse (an encoding they do not know, a stream that fails its checks), more than 8
+    channels — goes the way `load_audio(file, sr)` goes, ffmpeg first, and comes back as samples."""
+    kind, parsed = _sniff(file), None
+    if kind == "wav":
+        parsed = _parse_wav(file)
+    elif kind == "flac":
+        try:
+            parsed = _parse_flac(file)
+        except RuntimeError:                              # the host route decides: ffmpeg may read it, else it raises the same
+            parsed = None
+    if parsed is not None and 1 <= parsed[0].shape[1] <= MAX_DEVICE_CHANNELS:
+        return parsed
+    return load_audio(file, sr)
+
+
+def _ingest_device(staged, file: str, sr: int, device: torch.device) -> torch.Tensor:
+    """Device half: upload the PCM in its stored width, then down-mix + resample + quantise in one kernel (hip.resample) on
+    the calling thread's current stream; samples that came from the host route are uploaded as they are."""
+    if isinstance(staged, tuple):
+        pcm, rate, bits = staged
+        try:
+            pcm = np.require(pcm, requirements=["C", "A", "W"])     # a copy only for a sample array at an odd file offset
+            return hip.resample(torch.from_numpy(pcm).to(device), rate, sr, bits)
+        except hip.HipLimitError:                         # a rate pair whose filter the kernel does not take
+            staged = load_audio(file, sr)
+    return torch.from_numpy(staged).to(device)
+
+
+def load_audio(file: str, sr: int = SAMPLE_RATE, device: Optional[Union[str, torch.device]] = None):
     """Decode `file` to mono float32 at `sr` Hz.  Same contract as the reference (audio.py:25-62): ffmpeg does
     the decoding / down-mixing / resampling; a RuntimeError is raised when it fails.  When the ffmpeg binary
     does not exist, RIFF/WAVE files are read natively and FLAC files through the native decoder of
-    csrc/flac_decode.c (frame CRCs and the stream's MD5 signature are verified)."""
+    csrc/flac_decode.c (frame CRCs and the stream's MD5 signature are verified).
+
+    `device` (a GPU; no counterpart in the reference): the result is a torch.float32 tensor on that device, and WAV / FLAC
+    files never touch ffmpeg or scipy — they are parsed natively, the stored PCM is uploaded and one HIP kernel
+    (csrc/resample.hip) does the down-mix, the polyphase resampling and the 16-bit quantisation in float64.  It evaluates the
+    same filter as the NATIVE host route (scipy's resample_poly, taken when ffmpeg is absent), which accumulates in float32:
+    those two agree to one 16-bit step, on all but about 0.1 % of the samples exactly.  Against ffmpeg's own
+    resampler — the host route where ffmpeg is installed — no bound is claimed or has been measured: it is a different
+    filter, as it always was for the native route.  Other containers, WAV / FLAC files the native readers refuse, files with
+    more than 8 channels and rate pairs whose filter the kernel does not take go the host route (ffmpeg first) and are
+    uploaded.  hip.HipError without a GPU."""
+    if device is not None:
+        device = torch.device(device)
+        hip.require_gpu(device)
+        return _ingest_device(_ingest_host(file, sr), file, sr, device)
     cmd = ["ffmpeg", "-nostdin", "-threads", "0", "-i", file, "-f", "s16le", "-ac", "1",
            "-acodec", "pcm_s16le", "-ar", str(sr), "-"]
     try:

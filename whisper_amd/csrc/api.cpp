@@ -1720,3 +1720,32 @@ extern "C" int wh_speech_cuts(const float* level, int64_t content_frames, int mi
   HIPCHK(e);
   return WH_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// device-side audio ingest (resample.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int wh_resample(const void* pcm, int sample_format, int bits, int channels, int64_t n_frames, const double* taps,
+                           int up, int down, int half_len, float* out, int64_t n_out, void* stream) {
+  if (!pcm || !taps || !out) return WH_ERR_ARG;
+  if (channels < 1 || channels > 8 || n_frames < 0 || n_frames > ((int64_t)1 << 38) || half_len < 0) return WH_ERR_ARG;
+  if (up < 1 || down < 1 || up > (1 << 24) || down > (1 << 24)) return WH_ERR_ARG;
+  for (int a = up, b = down; b != 0;) {              // up / down must be in lowest terms
+    const int r = a % b;
+    a = b;
+    b = r;
+    if (b == 0 && a != 1) return WH_ERR_ARG;
+  }
+  switch (sample_format) {
+    case WH_PCM_U8: if (bits != 8) return WH_ERR_ARG; break;
+    case WH_PCM_S16: if (bits < 1 || bits > 16) return WH_ERR_ARG; break;
+    case WH_PCM_S32: if (bits < 1 || bits > 32) return WH_ERR_ARG; break;
+    case WH_PCM_F32: case WH_PCM_F64: break;
+    default: return WH_ERR_ARG;
+  }
+  if (n_out != (n_frames * up + down - 1) / down) return WH_ERR_ARG;
+  if (2 * (int64_t)half_len + 1 > WH_RESAMPLE_MAX_TAPS || resample_outputs_per_wg(up, down, half_len) < 1) return WH_ERR_LIMIT;
+  if (n_frames == 0) return WH_OK;
+  HIPCHK(launch_resample(pcm, sample_format, bits, channels, n_frames, taps, up, down, half_len, out, n_out,
+                         (hipStream_t)stream));
+  return WH_OK;
+}

@@ -354,4 +354,13 @@ hipError_t launch_frame_level(const float* mel, int n_mels, int64_t frame_stride
 hipError_t launch_speech_cuts(const float* level, int content, int min_frames, int max_frames, int guard, float* cost,
                               int* cuts, int* n_cuts, int max_cuts, hipStream_t stream);
 
+// ---- resample.hip --------------------------------------------------------------------------
+// interleaved PCM [n_frames][channels] (format: WH_PCM_* of include/whisper_hip.h; bits: full scale 2^(bits-1) of the signed
+// integer formats) -> mono fp32 [n_out] on the 16-bit grid: down-mix, polyphase resampling with taps [2 * half + 1] (float64,
+// device), quantisation — all in float64 (definitions at the top of resample.hip)
+hipError_t launch_resample(const void* pcm, int format, int bits, int channels, int64_t n_frames, const double* taps, int up,
+                           int down, int half, float* out, int64_t n_out, hipStream_t stream);
+// outputs one workgroup takes so that the input span they reach fits its LDS; 0: not even one fits (down / up too large)
+int resample_outputs_per_wg(int up, int down, int half);
+
 }  // namespace whk

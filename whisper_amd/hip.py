@@ -31,10 +31,16 @@ WH_WEIGHTS_ENC_QK_SCALED = 2
 # sqrt(0.125 * log2 e): with it in both the query and the key projection, K.Q^T is the exp2 argument of the softmax
 ENC_QK_SCALE = (0.125 * 1.4426950408889634) ** 0.5
 MEL_SCRATCH_BYTES = 2048
+WH_PCM_U8, WH_PCM_S16, WH_PCM_S32, WH_PCM_F32, WH_PCM_F64 = 0, 1, 2, 3, 4
+RESAMPLE_MAX_TAPS = 1 << 23         # WH_RESAMPLE_MAX_TAPS: longest filter wh_resample takes
 
 
 class HipError(RuntimeError):
     pass
+
+
+class HipLimitError(HipError):
+    """status 5 (WH_ERR_LIMIT): the arguments are valid but exceed a compiled-in limit of the library"""
 
 
 class Dims(C.Structure):
@@ -88,6 +94,8 @@ SIGNATURES = {
     "wh_last_hip_error": (C.c_int, []),
     "wh_last_hip_error_string": (C.c_char_p, []),
     "wh_log_mel": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "wh_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                              C.c_void_p, C.c_int64, C.c_void_p]),
     "wh_model_create": (C.c_int, [C.POINTER(Dims), C.c_int, C.POINTER(ModelWeights), C.POINTER(C.c_void_p)]),
     "wh_model_destroy": (None, [C.c_void_p]),
     "wh_encoder_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
@@ -155,6 +163,7 @@ def lib():
     return _LIB
 
 
+WH_ERR_LIMIT = 5
 WH_ERR_HANDOFF = 6
 WH_RUNNING = 7                      # wh_task_poll: the loop begun with wh_task_*_begin has not ended yet
 
@@ -165,7 +174,7 @@ def check(rc: int, what: str = "") -> None:
         msg = L.wh_status_string(rc).decode()
         if rc == 3:
             msg += f" ({L.wh_last_hip_error_string().decode()})"
-        raise HipError(f"{what or 'libwhisper_hip'}: {msg}")
+        raise (HipLimitError if rc == WH_ERR_LIMIT else HipError)(f"{what or 'libwhisper_hip'}: {msg}")
 
 
 def require_gpu(device: torch.device) -> None:
@@ -932,6 +941,61 @@ def log_mel(audio: torch.Tensor, filters: torch.Tensor) -> torch.Tensor:
     check(lib().wh_log_mel(a.data_ptr(), n, B, n_mels, filters.data_ptr(), out.data_ptr(), scratch.data_ptr(),
                            stream_ptr(s)), "wh_log_mel")
     return out[0] if single else out
+
+
+_PCM_FORMATS = {torch.uint8: (WH_PCM_U8, 8), torch.int16: (WH_PCM_S16, 16), torch.int32: (WH_PCM_S32, 32),
+                torch.float32: (WH_PCM_F32, 0), torch.float64: (WH_PCM_F64, 0)}
+_RESAMPLE_TAPS: Dict[Tuple[int, int, torch.device], torch.Tensor] = {}
+_RESAMPLE_LOCK = threading.Lock()
+
+
+def _resample_taps(rate: int, sr: int, device: torch.device) -> torch.Tensor:
+    """the filter of (rate -> sr) as float64 on `device`: built once by audio.resample_taps, then kept there"""
+    device = torch.device(device.type, torch.cuda.current_device() if device.index is None else device.index)
+    key = (rate, sr, device)
+    with _RESAMPLE_LOCK:
+        taps = _RESAMPLE_TAPS.get(key)
+        if taps is None:
+            from .audio import resample_taps
+            taps = _RESAMPLE_TAPS[key] = torch.from_numpy(resample_taps(rate, sr).copy()).to(device)   # (the cached array is read-only)
+    return taps
+
+
+def resample(pcm: torch.Tensor, rate: int, sr: int = 16000, bits: Optional[int] = None) -> torch.Tensor:
+    """Interleaved PCM on the GPU as a WAV / FLAC reader holds it — uint8 (8-bit WAV, offset 128), int16, int32 (`bits` = the
+    stored sample width: full scale 2^(bits-1), default the dtype's), float32 or float64, [n_frames][channels] or [n_frames],
+    1 - 8 channels — at `rate` Hz -> mono float32 [ceil(n_frames * sr / rate)] at `sr` Hz on the 16-bit grid: equal-weight
+    down-mix, the polyphase resampling of scipy.signal.resample_poly and the 16-bit quantisation, evaluated in float64 by one
+    kernel (wh_resample, csrc/resample.hip).  `rate == sr`: down-mix and quantisation only.  Raises HipLimitError for a
+    rate pair the kernel does not take: a filter of more than RESAMPLE_MAX_TAPS taps (20 * max(up, down) + 1, up / down =
+    sr / rate in lowest terms), or down / up so large (about 200) that the input span of one output exceeds a workgroup's
+    LDS; HipError for more than 8 channels or rate / sr above 2^24 after reduction."""
+    require_gpu(pcm.device)
+    if pcm.dtype not in _PCM_FORMATS or pcm.dim() not in (1, 2):
+        raise ValueError(f"resample: unsupported PCM tensor ({pcm.dtype}, {pcm.dim()} dimensions)")
+    rate, sr = int(rate), int(sr)
+    if rate < 1 or sr < 1:
+        raise ValueError(f"resample: rates must be positive (got {rate} -> {sr})")
+    fmt, width = _PCM_FORMATS[pcm.dtype]
+    bits = width if bits is None else int(bits)
+    x = (pcm[:, None] if pcm.dim() == 1 else pcm).contiguous()
+    n, channels = x.shape
+    import math
+    g = math.gcd(rate, sr)
+    up, down = sr // g, rate // g
+    half = 0 if up == down else 10 * max(up, down)
+    if 2 * half + 1 > RESAMPLE_MAX_TAPS:
+        raise HipLimitError(f"resample: the filter of {rate} -> {sr} Hz has {2 * half + 1} taps (limit {RESAMPLE_MAX_TAPS})")
+    n_out = -(-n * up // down)
+    out = torch.empty(n_out, dtype=torch.float32, device=x.device)
+    if n == 0:
+        return out
+    with torch.cuda.device(x.device):                       # the library launches on the calling thread's current device
+        taps = _resample_taps(rate, sr, x.device)
+        s = torch.cuda.current_stream(x.device)
+        check(lib().wh_resample(x.data_ptr(), fmt, bits, channels, n, taps.data_ptr(), up, down, half, out.data_ptr(), n_out,
+                                stream_ptr(s)), "wh_resample")
+    return out
 
 
 def median_filter(x: torch.Tensor, width: int) -> torch.Tensor:

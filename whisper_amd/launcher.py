@@ -100,12 +100,15 @@ def _audio_cost(audio) -> float:
     return float(getattr(audio, "shape", [1])[-1])
 
 
-def transcribe_sharded(model, audios: Sequence[Any], dist=None, *, batch_size: int = 24, **kwargs) -> Optional[List[dict]]:
+def transcribe_sharded(model, audios: Sequence[Any], dist=None, *, batch_size: int = 24, device_ingest: bool = False,
+                       **kwargs) -> Optional[List[dict]]:
     """Many files over many GPUs: every rank transcribes its cost-balanced share with `transcribe_batch` (windows of
     one file never leave their rank: seek and prompt depend on the previous window, transcribe.py:288-293,371-399);
     rank 0 returns the result dicts in input order, other ranks None.  All inputs must be of one kind (arrays or
-    paths) for the costs to be comparable."""
+    paths) for the costs to be comparable.  `device_ingest`: every rank loads its files on its own GPU (transcribe_batch)."""
     from .transcribe import transcribe_batch
     costs = [_audio_cost(a) for a in audios]
+    if device_ingest:
+        kwargs = dict(kwargs, device_ingest=True)
     return run_balanced(list(audios), costs, lambda part: transcribe_batch(model, part, batch_size=batch_size, **kwargs),
                         dist)

@@ -392,7 +392,12 @@ def transcribe(
     (whisper/transcribe.py:38-125): returns {"text", "segments", "language"}; `decode_options` are forwarded to
     `DecodingOptions`; `temperature` may be a tuple of fallback temperatures; `clip_timestamps` selects
     start,end,start,end,... ranges in seconds; `word_timestamps` adds per-word timing from cross-attention + DTW.
+    `device_ingest: bool = False` (no counterpart in the reference, so it travels among the keywords and the parameter list
+    stays the reference's): a file path is loaded with `audio.load_audio(path, device=model.device)` — WAV / FLAC are
+    down-mixed, resampled and quantised on the GPU; arrays and tensors are untouched.
     """
+    if decode_options.pop("device_ingest", False) and isinstance(audio, str):
+        audio = load_audio(audio, device=model.device)
     return _Transcriber(
         model, verbose, temperature, compression_ratio_threshold, logprob_threshold, no_speech_threshold,
         condition_on_previous_text, initial_prompt, carry_initial_prompt, word_timestamps, prepend_punctuations,
@@ -436,26 +441,36 @@ def _prompt_batches(model: "Whisper", options: DecodingOptions, prompts: List[Op
     return [rows[at: at + batch_size] for rows in classes.values() for at in range(0, len(rows), batch_size)]
 
 
-def _load_all(audios) -> list:
+def _load_all(audios, device: Optional[torch.device] = None) -> list:
     """decode the inputs that are file paths concurrently (ffmpeg subprocesses / the native FLAC decoder release the
-    GIL) instead of one after the other at the start of every file's state machine; arrays pass through untouched"""
+    GIL) instead of one after the other at the start of every file's state machine; arrays pass through untouched.
+    `device` (device-side ingest): the pool only parses / decodes the files to their stored PCM; the upload and the
+    resampling kernel of every file run on the calling thread and its current stream, in input order."""
     paths = [i for i, a in enumerate(audios) if isinstance(a, str)]
     out = list(audios)
     if len(paths) == 0:
         return out
+    if device is not None:
+        from . import hip
+        from .audio import _ingest_device, _ingest_host
+        hip.require_gpu(torch.device(device))
+        host, finish = (lambda i: _ingest_host(out[i], SAMPLE_RATE)), (
+            lambda i, staged: _ingest_device(staged, out[i], SAMPLE_RATE, torch.device(device)))
+    else:
+        host, finish = (lambda i: load_audio(out[i])), (lambda i, samples: samples)
     if len(paths) == 1:
-        out[paths[0]] = load_audio(out[paths[0]])
+        out[paths[0]] = finish(paths[0], host(paths[0]))
         return out
     from concurrent.futures import ThreadPoolExecutor
     from .utils import usable_cores
     with ThreadPoolExecutor(max(1, min(len(paths), usable_cores(), 16))) as pool:
-        for i, samples in zip(paths, pool.map(lambda i: load_audio(out[i]), paths)):
-            out[i] = samples
+        for i, staged in zip(paths, pool.map(host, paths)):
+            out[i] = finish(i, staged)
     return out
 
 
 def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_active_files: Optional[int] = None,
-                     in_flight: int = 1, **kwargs) -> List[dict]:
+                     in_flight: int = 1, device_ingest: bool = False, **kwargs) -> List[dict]:
     """Transcribe several files at once (no counterpart in the reference, which is strictly
     one file at a time).  Every file keeps its own seek / prompt / fallback state machine exactly as `transcribe`;
     the driver advances them in lock-step and decodes the windows that are pending at the same moment — and whose
@@ -480,7 +495,9 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
     applies per group; an explicit `max_active_files` is divided between the groups, so that bound on resident spectrograms holds
     for the call as a whole (the default is 2 * batch_size per group), while each group keeps its own cached decoding tasks (workspaces scale with the number of groups).  Prefer
     a larger `batch_size` (rows per decode chain, up to 24) over more groups when there are enough files: a wider chain streams
-    the decoder's weights once for all its rows.  Worth it from about 2 * batch_size files on."""
+    the decoder's weights once for all its rows.  Worth it from about 2 * batch_size files on.
+    `device_ingest`: file paths are loaded as `load_audio(path, device=model.device)` loads them (WAV / FLAC down-mixed,
+    resampled and quantised on the GPU); the host-side parsing / FLAC decoding stays on the loader threads."""
     audios = list(audios)
     if in_flight > 1 and len(audios) > 1:
         from .decoding import run_in_lanes
@@ -493,7 +510,7 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
 
         def job(ids):
             return lambda: transcribe_batch(model, [audios[i] for i in ids], batch_size=batch_size,
-                                            max_active_files=per_group, in_flight=1, **kwargs)
+                                            max_active_files=per_group, in_flight=1, device_ingest=device_ingest, **kwargs)
         parts = run_in_lanes(model, [job(ids) for ids in groups], n, torch.float16 if fp16 else torch.float32)
         merged: List[Optional[dict]] = [None] * len(audios)
         for ids, part in zip(groups, parts):
@@ -514,7 +531,7 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
     def start(take: List[int]) -> list:
         """only the files admitted are decoded to PCM and hold a whole-file spectrogram on the device, so memory follows the
         window of active files, not the total audio duration"""
-        loaded = _load_all([audios[i] for i in take])
+        loaded = _load_all([audios[i] for i in take], model.device if device_ingest else None)
         mels = [None] * len(take)
         if detect:
             # language identification (transcribe.py:139-152) of the admitted files in batched passes instead of one
@@ -661,7 +678,7 @@ def plan_chunks(mel: torch.Tensor, content_frames: int, min_chunk_s: float = 15.
 
 
 def transcribe_chunked(model: "Whisper", audio: Union[str, np.ndarray, torch.Tensor], *, batch_size: int = 24,
-                       min_chunk_s: float = 15.0, guard_s: float = 0.1, **kwargs) -> dict:
+                       min_chunk_s: float = 15.0, guard_s: float = 0.1, device_ingest: bool = False, **kwargs) -> dict:
     """Transcribe ONE long recording with a wide decode chain (no counterpart in the reference, whose windows are strictly
     sequential: every window's seek and prompt depend on the tokens of the one before, so `transcribe` decodes an hour of
     audio as a 1-row chain).  The file is cut at pauses into chunks of `min_chunk_s` to 30 s (`plan_chunks`: chosen on the
@@ -680,6 +697,7 @@ def transcribe_chunked(model: "Whisper", audio: Union[str, np.ndarray, torch.Ten
       * `clip_timestamps` cannot be combined with chunking (ValueError), nor can `min_chunk_s` outside (0, 30] or `guard_s`
         above 0.64 (the cut kernel's halo);
       * `verbose=True` prints the segments chunk by chunk in completion order, not in file order; there is no progress bar.
+    `device_ingest`: a file path is loaded with `load_audio(path, device=model.device)`, as in `transcribe`.
 
     Returns the dict `transcribe` returns — `segments` concatenated in chunk order with `id` renumbered, `text` the
     concatenation of the chunks' texts, `language` — plus `chunks`: `[(start_s, end_s), ...]`.  A file of at most 30 s has no
@@ -690,6 +708,8 @@ def transcribe_chunked(model: "Whisper", audio: Union[str, np.ndarray, torch.Ten
     if batch_size < 1:
         raise ValueError(f"batch_size must be at least 1 (got {batch_size})")
     fixed = {k: kwargs.pop(k, default) for k, default in _WALK_DEFAULTS.items()}
+    if device_ingest and isinstance(audio, str):
+        audio = load_audio(audio, device=model.device)
     mel = log_mel_spectrogram(audio, model.dims.n_mels, padding=N_SAMPLES, device=model.device)
     plan = plan_chunks(mel, mel.shape[-1] - N_FRAMES, min_chunk_s, guard_s)
     chunks = [(a / FRAMES_PER_SECOND, b / FRAMES_PER_SECOND) for a, b in plan]
