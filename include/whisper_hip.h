@@ -222,6 +222,29 @@ int wh_task_set_audio(wh_task *t, const void *features, void *stream);
  * May be called repeatedly (T0 >= 1) to append teacher-forced tokens; n_rows = n_audio * n_group. */
 int wh_task_prefill(wh_task *t, const int64_t *tokens, int64_t token_stride, int T0,
                     const int32_t *sel_pos, int n_sel, float *logits_out, void *stream);
+/* Teacher-forced scoring: wh_task_prefill of T0 tokens per row whose selected positions first .. T0 - 2 are turned into
+ * log-probabilities of the token that follows them, without the logits reaching memory (a fused tied-embedding
+ * projection + log-sum-exp + target gather; the reference's route is `F.log_softmax(logits, -1)` and a gather, as in
+ * decoding.py:283-285 and timing.py:199-204).  Caches are filled at the same positions and the position advances by T0 as
+ * in wh_task_prefill, and WH_TASK_CAPTURE_Q tasks capture their queries the same way.  Scoring always runs the GEMM form of
+ * the pass, so that a row's numbers do not depend on what it is batched with: caches, captured queries and scores are
+ * bit-identical to wh_task_prefill's where that call takes the GEMM form too (n_rows * T0 > 96), and equal to it within
+ * rounding (not bitwise) for the smaller shapes that wh_task_prefill runs on its few-row kernels.
+ *   tokens: int64 [n_rows][token_stride] device; n_tok: HOST int32 [n_rows], valid length of each row in [1, T0];
+ *   n_out = T0 - 1 - first; outputs fp32 / int32 [n_rows][n_out] device: entry [r][p - first] scores tokens[r][p + 1]
+ *   from position p over the vocabulary entries below v_end (1 <= v_end <= n_vocab):
+ *     logprob      logit of that token minus the log-sum-exp (-inf if the token id is >= v_end)
+ *     top_logprob  the largest logit minus the same log-sum;  top_token: the lowest id that attains it
+ *   Slots with p + 1 >= n_tok[r] are padding: logprob = 0, top_logprob = 0, top_token = -1.
+ *   top_logprob_out / top_token_out may be NULL.  scratch: device, 16-byte aligned, wh_score_scratch_bytes(m, n_rows,
+ *   n_out) bytes (0 for a NULL model).  Results are bit-identical from run to run.
+ * WH_ERR_ARG: null pointers, first outside [0, T0 - 2], v_end outside [1, n_vocab], an n_tok[r] outside [1, T0];
+ * WH_ERR_WORKSPACE: scratch too small; WH_ERR_STATE: ragged prompts (wh_task_set_lag) or a begun loop pending — all
+ * before any device work. */
+size_t wh_score_scratch_bytes(const wh_model *m, int n_rows, int n_pos);
+int wh_task_score(wh_task *t, const int64_t *tokens, int64_t token_stride, int T0, const int32_t *n_tok,
+                  int first, int v_end, float *logprob_out, float *top_logprob_out, int32_t *top_token_out,
+                  void *scratch, size_t scratch_bytes, void *stream);
 /* Later Inference.logits calls (decoding.py:159-163): one new token per row.
  *   last_tokens: int64 device, row r at last_tokens[r*token_stride]; logits_out: fp32 [n_rows][n_vocab]. */
 int wh_task_step(wh_task *t, const int64_t *last_tokens, int64_t token_stride, float *logits_out,

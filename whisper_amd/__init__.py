@@ -22,8 +22,8 @@ import torch
 from . import audio as _audio
 from .audio import SAMPLE_RATE as _SAMPLE_RATE
 from .audio import log_mel_spectrogram, pad_or_trim
-from .decoding import (DecodingOptions, DecodingResult, decode, decode_many, detect_language, run_in_lanes,
-                       run_interleaved)
+from .decoding import (DecodingOptions, DecodingResult, ScoreResult, decode, decode_many, detect_language, run_in_lanes,
+                       run_interleaved, score)
 from .model import ModelDimensions, Whisper
 from .registry import ALIGNMENT_HEADS as _ALIGNMENT_HEADS
 from .registry import MODEL_URLS as _MODELS

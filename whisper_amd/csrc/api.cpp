@@ -645,8 +645,28 @@ static hipError_t proj_resid(const wh_model* m, const void* x, int64_t x_ld, int
 // per segment — row b G of the caller's token matrix — runs through the decoder; it uses cache rows / logits rows
 // 0 .. B-1, and the caller replicates them to the rows of each group afterwards (replicate_leader_rows).  The reference
 // feeds all n_audio x n_group identical rows (decoding.py:734 repeat_interleave): same values, G times the work.
+// sc (wh_task_score): positions first .. T0 - 2 of every row go through the fused projection + log-sum-exp + target gather
+// (score.hip) instead of producing logits; everything before the final LayerNorm is the same pass.
+struct ScoreReq {
+  const int32_t* n_tok; int first, v_end;
+  float* logprob; float* top_logprob; int32_t* top_token;
+  void* scratch; size_t scratch_bytes;
+};
+// caller scratch of wh_task_score: [targets int32 [Ms]] [one partial per (selected row, vocabulary slice)]
+static size_t score_carve(size_t Ms, int V, void* base, int** target, void** part, size_t* part_bytes) {
+  Carver c(base);
+  int* tg = (int*)c.take(Ms * 4);
+  const size_t pb = score_scratch_bytes((int64_t)Ms, V);
+  void* pp = c.take(pb);
+  if (target) *target = tg;
+  if (part) *part = pp;
+  if (part_bytes) *part_bytes = pb;
+  return align_up(c.off, 256);
+}
+
 static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride, int T0, const int32_t* sel_pos,
-                        int n_sel, float* logits_out, int64_t logits_row_ld, hipStream_t s, bool leaders = false) {
+                        int n_sel, float* logits_out, int64_t logits_row_ld, hipStream_t s, bool leaders = false,
+                        const ScoreReq* sc = nullptr) {
   const wh_model* m = t->m;
   const wh_dims& d = m->d;
   const int D = d.n_text_state, H = d.n_text_head, C = d.n_text_ctx, Ta = d.n_audio_ctx, V = d.n_vocab;
@@ -663,7 +683,8 @@ static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride,
     for (int r = 0; r < R; ++r) if (t->h_lag[r * lag_step] >= T0) return WH_ERR_ARG;
   }
 
-  const bool skinny = M <= SKINNY_ROWS && D <= 2048;
+  // scoring always takes the GEMM path: a row's numbers then do not depend on how many rows it was batched with
+  const bool skinny = !sc && M <= SKINNY_ROWS && D <= 2048;
   // one row per audio (alignment tasks; beam search through its leader rows) and a transposed V: flash cross attention
   const bool no_flash = WH_DEV_FLAG("WH_NO_PREFILL_FLASH");   // developer A/B switch
   const bool flash_cross = !skinny && !no_flash && m->dtype == WH_F16 && t->cross_vt && Gp == 1 && R == t->B &&
@@ -747,8 +768,27 @@ static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride,
       HIPCHK(gemm(m, t->h, 4 * D, L.fc2_w, 4 * D, t->x, D, M, D, L.fc2_b, 0, t->x, D, true, s));
     }
   }
-  // logits of the selected positions
-  if (logits_out && n_sel > 0) {
+  if (sc) {
+    // selected rows and valid lengths go through the task's pinned words in one copy (see below): [Ms rows][R lengths],
+    // Ms = R (T0 - 1 - first) <= R (Tmax - 1)
+    const int n_out = T0 - 1 - sc->first, Ms = R * n_out;
+    if (!t->h_sel) HIPCHK(hipHostMalloc((void**)&t->h_sel, (size_t)t->R * t->Tmax * sizeof(int), hipHostMallocDefault));
+    if (!t->sel_event) HIPCHK(hipEventCreateWithFlags(&t->sel_event, hipEventDisableTiming));
+    else HIPCHK(hipEventSynchronize(t->sel_event));
+    int* sel = t->h_sel;
+    for (int r = 0; r < R; ++r)
+      for (int i = 0; i < n_out; ++i) sel[(size_t)r * n_out + i] = r * T0 + sc->first + i;
+    for (int r = 0; r < R; ++r) sel[(size_t)Ms + r] = sc->n_tok[r];
+    HIPCHK(hipMemcpyAsync(t->d_sel, sel, (size_t)(Ms + R) * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(t->sel_event, s));
+    int* target; void* part; size_t part_bytes;
+    score_carve((size_t)Ms, V, sc->scratch, &target, &part, &part_bytes);
+    HIPCHK(launch_score_targets(tokens, token_stride, t->d_sel + Ms, R, n_out, sc->first, target, s));
+    HIPCHK(launch_gather_rows(t->x, t->d_sel, Ms, D, t->xsel, s));
+    HIPCHK(launch_layernorm(t->xsel, D, m->w.dec_ln_w, m->w.dec_ln_b, t->xseln, D, Ms, D, m->dtype, s));
+    HIPCHK(launch_score(t->xseln, D, m->w.tok_emb, D, target, Ms, D, V, sc->v_end, sc->logprob, sc->top_logprob,
+                        sc->top_token, part, part_bytes, m->dtype, s));
+  } else if (logits_out && n_sel > 0) {        // logits of the selected positions
     // the row indices go through pinned memory the task owns, so that the copy needs no host synchronisation behind it (the
     // fused loops' begin calls must not wait for the device); an earlier call's copy has to have executed before the words
     // are rewritten — it has, unless calls follow each other faster than the stream drains
@@ -792,6 +832,27 @@ extern "C" int wh_task_prefill(wh_task* t, const int64_t* tokens, int64_t token_
   if (!t || !tokens) return WH_ERR_ARG;
   if (!sel_pos) n_sel = T0;
   return prefill_impl(t, tokens, token_stride, T0, sel_pos, n_sel, logits_out, t->m->d.n_vocab, (hipStream_t)stream);
+}
+
+extern "C" size_t wh_score_scratch_bytes(const wh_model* m, int n_rows, int n_pos) {
+  if (!m || n_rows <= 0 || n_pos <= 0) return 0;
+  return score_carve((size_t)n_rows * n_pos, m->d.n_vocab, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int wh_task_score(wh_task* t, const int64_t* tokens, int64_t token_stride, int T0, const int32_t* n_tok,
+                             int first, int v_end, float* logprob_out, float* top_logprob_out, int32_t* top_token_out,
+                             void* scratch, size_t scratch_bytes, void* stream) {
+  TASK_ENTER(t);
+  if (!t || !tokens || !n_tok || !logprob_out || !scratch) return WH_ERR_ARG;
+  if (first < 0 || first > T0 - 2 || v_end < 1 || v_end > t->m->d.n_vocab) return WH_ERR_ARG;
+  if (T0 > t->Tmax || t->pos + T0 > t->m->d.n_text_ctx) return WH_ERR_ARG;
+  for (int r = 0; r < t->R; ++r) if (n_tok[r] < 1 || n_tok[r] > T0) return WH_ERR_ARG;
+  if (t->lag_on) return WH_ERR_STATE;          // ragged prompts shift the selected positions per row: not scored
+  if ((((uintptr_t)scratch) & 15) != 0) return WH_ERR_ARG;
+  const size_t Ms = (size_t)t->R * (T0 - 1 - first);
+  if (score_carve(Ms, t->m->d.n_vocab, nullptr, nullptr, nullptr, nullptr) > scratch_bytes) return WH_ERR_WORKSPACE;
+  ScoreReq sc = {n_tok, first, v_end, logprob_out, top_logprob_out, top_token_out, scratch, scratch_bytes};
+  return prefill_impl(t, tokens, token_stride, T0, nullptr, 0, nullptr, 0, (hipStream_t)stream, false, &sc);
 }
 
 static inline void* cross_layer(const wh_task* t, int l);

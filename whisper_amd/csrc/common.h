@@ -166,6 +166,26 @@ __device__ __forceinline__ float wave_max(float v) {
 __device__ __forceinline__ int swz_unit(int row, int unit) { return unit ^ ((row >> 1) & 7); }
 __device__ __forceinline__ int swz_byte(int row, int unit) { return row * 128 + (swz_unit(row, unit) << 4); }
 
+// ---------------------------------------------------------------------------------------------
+// building blocks of the LDS-staged MFMA K loops (gemm.hip, score.hip): one 16x16 tile step over a 16-byte unit of K per
+// lane, the 16-byte global -> LDS copy (wave-uniform LDS base + lane * 16), and a counted wait for it
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void mma16(half8v a, half8v b, float4v& c) {
+  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ void mma16(float4v a, float4v b, float4v& c) {
+  // lane (i, g) holds k = 16q + 4g + e in element e: step e sums the four k of the four lane groups
+  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
+}
+__device__ __forceinline__ void glds16(const void* g, char* lds_uniform) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                   (__attribute__((address_space(3))) void*)lds_uniform, 16, 0, 0);
+}
+template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
 // ordered-int encoding of floats so that atomicMax on int32 orders like float
 __device__ __forceinline__ int float_to_ordered(float f) {
   int i = __float_as_int(f);

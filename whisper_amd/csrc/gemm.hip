@@ -25,22 +25,6 @@
 
 namespace {
 
-__device__ __forceinline__ void mma16(half8v a, half8v b, float4v& c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ void mma16(float4v a, float4v b, float4v& c) {
-  // lane (i, g) holds k = 16q + 4g + e in element e: step e sums the four k of the four lane groups
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void glds16(const void* g, char* lds_uniform) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_uniform, 16, 0, 0);
-}
-
 template <typename OutT> struct Out4;
 template <> struct Out4<float> {
   static __device__ __forceinline__ void store(float* p, float4v v) { *(float4v*)p = v; }
@@ -52,7 +36,6 @@ template <> struct Out4<half_t> {
   }
 };
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void order_memory_ops() { asm volatile("" ::: "memory"); }
 
 constexpr int FM = 4, FN = 4;            // MFMA 16x16 tiles per wave: a 64x64 block

@@ -363,4 +363,22 @@ hipError_t launch_resample(const void* pcm, int format, int bits, int channels, 
 // outputs one workgroup takes so that the input span they reach fits its LDS; 0: not even one fits (down / up too large)
 int resample_outputs_per_wg(int up, int down, int half);
 
+// ---- score.hip -----------------------------------------------------------------------------
+// Teacher-forced scoring without the logits.  xn [M][K] (element type, row stride ldx), W = tok_emb [V][K], target [M]
+// (device int32), 1 <= v_end <= V.  Per row m, over the columns v < v_end of logit = xn · Wᵀ:
+//   logprob[m] = logit[target[m]] - log sum exp(logit)      (-inf when target[m] >= v_end)
+//   top_logprob[m] / top_token[m] = the largest logit minus the same log-sum / the lowest id that attains it
+//   target[m] < 0 (padded slot): logprob = 0, top_logprob = 0, top_token = -1
+// top_logprob / top_token may be null.  scratch (16-byte aligned): score_scratch_bytes(M, V) bytes, one 16-byte partial
+// per (row, SCORE_BN-column slice); two launches, no atomics, bit-identical from run to run.  K % 64 == 0 (fp16) / % 32 (fp32).
+constexpr int SCORE_BN = 128;    // vocabulary columns per slice (one workgroup per 128 rows x one slice)
+constexpr int SCORE_WGN = 2;     // waves side by side across a slice
+size_t score_scratch_bytes(int64_t M, int V);
+hipError_t launch_score(const void* xn, int64_t ldx, const void* W, int64_t ldw, const int* target, int M, int K, int V,
+                        int v_end, float* logprob, float* top_logprob, int* top_token, void* scratch,
+                        size_t scratch_bytes, int dtype, hipStream_t stream);
+// target[r][i] = tokens[r * token_stride + first + i + 1] for i < n_out, or -1 where first + i + 1 >= n_tok[r] (all device)
+hipError_t launch_score_targets(const int64_t* tokens, int64_t token_stride, const int* n_tok, int R, int n_out, int first,
+                                int* target, hipStream_t stream);
+
 }  // namespace whk

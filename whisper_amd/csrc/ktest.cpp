@@ -94,4 +94,15 @@ int wht_replicate_row(void* base, int64_t layer_bytes, int n_layers, int64_t row
   return launch_replicate_row(base, layer_bytes, n_layers, row_bytes, src_row, dst_row0, G, used_bytes, (hipStream_t)stream);
 }
 
+// the fused projection + log-sum-exp + target gather (score.hip); wht_score_slice / wht_score_scratch_bytes: the slice
+// width the kernel's add chain follows from, and the partials it needs
+int wht_score_slice() { return SCORE_BN; }
+size_t wht_score_scratch_bytes(int64_t M, int V) { return score_scratch_bytes(M, V); }
+int wht_score(int dtype, const void* xn, int64_t ldx, const void* W, int64_t ldw, const int* target, int M, int K, int V,
+              int v_end, float* logprob, float* top_logprob, int* top_token, void* scratch, size_t scratch_bytes,
+              void* stream) {
+  return launch_score(xn, ldx, W, ldw, target, M, K, V, v_end, logprob, top_logprob, top_token, scratch, scratch_bytes,
+                      dtype, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -895,6 +895,133 @@ def decode(model: "Whisper", mel: Tensor, options: DecodingOptions = DecodingOpt
     return result[0] if single else result
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# teacher-forced scoring (no counterpart in the reference's API; its route is log_softmax + gather on full logits)
+# ---------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class ScoreResult:
+    tokens: List[int]                # the hypothesis as scored (strings encoded with the tokenizer)
+    token_logprobs: List[float]      # one per hypothesis token, then the closing <|endoftext|> (vocabulary="all")
+    sum_logprob: float
+    avg_logprob: float               # sum / (len(tokens) + 1), as DecodingTask.run computes it
+    top_tokens: List[int]            # the model's own arg-max at each scored position
+    top_logprobs: List[float]
+    language: str
+
+
+def _as_hypothesis_list(item, tokenizer: Tokenizer) -> List[List[int]]:
+    """hypotheses[b]: a list of token-id lists / strings, or ONE flat token-id list / string"""
+    def one(h) -> List[int]:
+        if isinstance(h, str):
+            return tokenizer.encode(" " + h.strip())
+        return [int(t) for t in (h.tolist() if torch.is_tensor(h) else h)]
+    if isinstance(item, str):
+        return [one(item)]
+    item = list(item)
+    if item and all(isinstance(t, (int, np.integer)) for t in item):
+        return [one(item)]
+    return [one(h) for h in item]
+
+
+@torch.no_grad()
+def score(model: "Whisper", mel: Tensor, hypotheses: Sequence, options: DecodingOptions = DecodingOptions(), *,
+          prompts: Optional[Sequence[Sequence[int]]] = None, vocabulary: str = "all",
+          batch_rows: int = 24) -> List[List[ScoreResult]]:
+    """How likely is this transcript given this audio: per-token log-probabilities of `hypotheses` under teacher forcing.
+
+    mel: (B, n_mels, 3000), a single (n_mels, 3000) mel, or encoder features, as `decode` accepts.  hypotheses[b]: the
+    candidate transcripts of clip b — token-id lists or strings (encoded with the tokenizer); one flat list / string per
+    clip is taken as a single hypothesis.  Every row starts from the tokens `DecodingTask._get_initial_tokens` builds
+    (language, task, prompt, prefix, without_timestamps, per-clip `prompts`; language=None detects it as `decode` does)
+    and is followed by the hypothesis and <|endoftext|>; the hypothesis tokens and that closing token are scored.
+    vocabulary="all": the distribution over every id; "text": over the ids below <|endoftext|> (the convention of
+    `timing.py`), the closing token is then not scored.
+
+    The numbers are the RAW model distribution: no SuppressTokens / SuppressBlank / timestamp rule is applied, so they
+    differ from a decode's sum_logprob wherever a filter removed probability mass.
+
+    The device never holds the (rows, positions, n_vocab) logits: wh_task_score (csrc/score.hip) reduces them on the fly.
+    Hypothesis counts are padded to the largest per clip (the task's n_group: the hypotheses of a clip share its
+    cross-attention K/V), clips are cut into chains of n_audio x n_group <= batch_rows rows, rows are right-padded to the
+    chain's longest.  Returns result[b][h]."""
+    if vocabulary not in ("all", "text"):
+        raise ValueError(f"vocabulary must be 'all' or 'text', not {vocabulary!r}")
+    if batch_rows < 1:
+        raise ValueError("batch_rows must be positive")
+    if mel.ndim == 2:
+        mel = mel.unsqueeze(0)
+    B = mel.shape[0]
+    if len(hypotheses) != B:
+        raise ValueError(f"{len(hypotheses)} hypothesis lists for {B} audio segments")
+    if prompts is not None and len(prompts) != B:
+        raise ValueError(f"{len(prompts)} prompts for {B} audio segments")
+    if options.task == "lang_id":
+        raise ValueError("score needs a transcribe / translate task")
+    task_opts = replace(options, beam_size=None, best_of=None, patience=None, temperature=0.0)
+    dt = DecodingTask(model, task_opts, prompts)
+    tokenizer, n_ctx = dt.tokenizer, model.dims.n_text_ctx
+    hyps = [_as_hypothesis_list(h, tokenizer) for h in hypotheses]
+    row_init = [list(r) for r in dt.row_tokens] if dt.row_tokens is not None else [list(dt.initial_tokens)] * B
+    for b in range(B):
+        for h in hyps[b]:
+            if len(row_init[b]) + len(h) + 1 > n_ctx:
+                raise ValueError(f"clip {b}: {len(row_init[b])} initial + {len(h)} hypothesis tokens + <|endoftext|> exceed "
+                                 f"n_text_ctx = {n_ctx}")
+            if any(t < 0 or t >= model.dims.n_vocab for t in h):
+                raise ValueError(f"clip {b}: token id outside the vocabulary")
+
+    features = dt._get_audio_features(mel)
+    languages = [options.language] * B
+    if options.language is None:
+        lang_tokens, lang_probs = model.detect_language(features, tokenizer)
+        languages = [max(p, key=p.get) for p in lang_probs]
+        lang_tokens = lang_tokens.tolist()
+        row_init = [list(r) for r in row_init]
+        for b in range(B):
+            row_init[b][row_init[b].index(tokenizer.sot) + 1] = int(lang_tokens[b])
+
+    eot = tokenizer.eot
+    v_end = model.dims.n_vocab if vocabulary == "all" else eot
+    results: List[List[Optional[ScoreResult]]] = [[None] * len(h) for h in hyps]
+    G = min(max([len(h) for h in hyps] + [1]), batch_rows)
+    # a unit = one clip with up to G of its hypotheses; a chain = as many units as fit batch_rows
+    units = [(b, list(range(k, min(k + G, len(hyps[b]))))) for b in range(B) for k in range(0, len(hyps[b]), G)]
+    per_chain = max(1, batch_rows // G)
+    engine = model.engine(features.dtype)
+    for c0 in range(0, len(units), per_chain):
+        chain = units[c0:c0 + per_chain]
+        rows, slots = [], []
+        for b, idx in chain:
+            for g in range(G):
+                h = hyps[b][idx[g]] if g < len(idx) else []          # filler rows score an empty hypothesis, unread
+                rows.append(row_init[b] + h + [eot])
+                slots.append((b, idx[g]) if g < len(idx) else None)
+        n_tok = [len(r) for r in rows]
+        T0 = max(n_tok)
+        first = min(len(row_init[b]) for b, _ in chain) - 1
+        tokens = torch.tensor([r + [eot] * (T0 - len(r)) for r in rows], device=features.device)
+        task = engine.acquire_task(len(chain), G, max(T0, 8))
+        try:
+            task.set_audio(features[[b for b, _ in chain]].contiguous())
+            logprob, top_lp, top_tok = task.score(tokens, n_tok, first, v_end)
+            logprob, top_lp, top_tok = logprob.cpu(), top_lp.cpu(), top_tok.cpu()
+        finally:
+            task.close()
+        for r, slot in enumerate(slots):
+            if slot is None:
+                continue
+            b, i = slot
+            h = hyps[b][i]
+            lo = len(row_init[b]) - 1 - first
+            n = len(h) + (1 if vocabulary == "all" else 0)
+            lp = logprob[r, lo:lo + n].tolist()
+            total = float(sum(lp))
+            results[b][i] = ScoreResult(tokens=list(h), token_logprobs=lp, sum_logprob=total,
+                                        avg_logprob=total / (len(h) + 1), top_tokens=top_tok[r, lo:lo + n].tolist(),
+                                        top_logprobs=top_lp[r, lo:lo + n].tolist(), language=languages[b])
+    return results
+
+
 def run_in_lanes(model: "Whisper", jobs: Sequence, in_flight: int = 3, dtype: Optional[torch.dtype] = None) -> list:
     """Call every job — a zero-argument callable that drives this model (log-mel, encoder, a decode loop, ...) — with up to
     `in_flight` of them running at once, each on a host thread and a HIP stream of its own (`HipModel.lane`); results in job

@@ -105,6 +105,9 @@ SIGNATURES = {
     "wh_task_destroy": (None, [C.c_void_p]),
     "wh_task_set_audio": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "wh_task_prefill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p]),
+    "wh_score_scratch_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "wh_task_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "wh_task_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "wh_task_rearrange": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "wh_task_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -655,11 +658,13 @@ class HipTask:
             self.handle = None
             self.ws = None
             self._align_scratch = None
+            self._score_scratch = None
 
     def held_bytes(self) -> int:
-        """device bytes this task keeps while it idles in its engine's task cache: the workspace + the alignment score slabs"""
-        extra = getattr(self, "_align_scratch", None)
-        return (0 if self.ws is None else self.ws.numel()) + (0 if extra is None else extra.numel())
+        """device bytes this task keeps while it idles in its engine's task cache: the workspace + the alignment score slabs
+        + the scoring partials (`score`)"""
+        extras = [getattr(self, "_align_scratch", None), getattr(self, "_score_scratch", None)]
+        return (0 if self.ws is None else self.ws.numel()) + sum(e.numel() for e in extras if e is not None)
 
     def __del__(self):
         try:
@@ -697,6 +702,36 @@ class HipTask:
                                         logits.data_ptr(), stream_ptr(self.stream)), "wh_task_prefill")
         tokens.record_stream(self.stream)
         return logits
+
+    def score(self, tokens: torch.Tensor, n_tok: Sequence[int], first: int, v_end: Optional[int] = None):
+        """wh_task_score: teacher-force `tokens` (int64 [n_rows][T0], device) like `prefill`, and score tokens[r][p + 1]
+        from position p for p in [first, T0 - 2] over the vocabulary ids below v_end (default: all) without the logits
+        reaching memory.  n_tok[r]: valid length of row r; slots with p + 1 >= n_tok[r] are padding (0, 0, -1).
+        Returns (logprob fp32, top_logprob fp32, top_token int32), each [n_rows][T0 - 1 - first] on the device."""
+        assert tokens.is_cuda and tokens.dtype == torch.int64 and tokens.dim() == 2
+        assert tokens.shape[0] == self.n_rows and tokens.stride(1) == 1 and len(n_tok) == self.n_rows
+        T0 = tokens.shape[1]
+        n_out = T0 - 1 - first
+        v_end = self.model.dims.n_vocab if v_end is None else int(v_end)
+        dev = tokens.device
+        need = lib().wh_score_scratch_bytes(self.model.handle, self.n_rows, max(n_out, 1))
+        # the partials belong to the task, as the alignment slabs do (align_batch): grown, never shrunk, released with it
+        scratch = getattr(self, "_score_scratch", None)
+        if scratch is None or scratch.numel() < need:
+            self._score_scratch = None
+            scratch = self._score_scratch = self.model._alloc(int(need))
+            scratch.record_stream(self.stream)
+        logprob = torch.empty(self.n_rows, max(n_out, 0), dtype=torch.float32, device=dev)
+        top_logprob = torch.empty_like(logprob)
+        top_token = torch.empty(self.n_rows, max(n_out, 0), dtype=torch.int32, device=dev)
+        arr = (C.c_int32 * self.n_rows)(*[int(v) for v in n_tok])
+        with self._call():
+            check(lib().wh_task_score(self.handle, tokens.data_ptr(), tokens.stride(0), T0, arr, int(first), v_end,
+                                      logprob.data_ptr(), top_logprob.data_ptr(), top_token.data_ptr(), scratch.data_ptr(),
+                                      scratch.numel(), stream_ptr(self.stream)), "wh_task_score")
+        for t_ in (tokens, logprob, top_logprob, top_token):
+            t_.record_stream(self.stream)
+        return logprob, top_logprob, top_token
 
     def step(self, last_tokens: torch.Tensor) -> torch.Tensor:
         """last_tokens: int64 view [n_rows] (any stride)."""
