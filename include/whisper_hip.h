@@ -262,6 +262,38 @@ int wh_task_reset(wh_task *t, void *stream);   /* stream-ordered (no host synchr
  * lag[r] earlier in row r; each decode step appends row r at cache position (position - lag[r]) and
  * wh_task_greedy writes row r's sampled tokens from column sample_begin - lag[r].  Cleared by wh_task_reset. */
 int wh_task_set_lag(wh_task *t, const int32_t *lag, void *stream);
+/* Phrase lists ("hotwords": contextual biasing by shallow fusion over a token trie; no counterpart in the reference, whose
+ * only handle is `initial_prompt`).  All phrases of a list sit in one trie, node 0 the root, in CSR form: the edges out of
+ * node n are [child_begin[n], child_begin[n + 1]), edge e is labelled child_token[e] (ascending and distinct within a node)
+ * and leads to child_node[e].  With a list set, wh_task_greedy / wh_task_greedy_begin keep one trie node per row:
+ *   - the node is the root when the row's first token is sampled;
+ *   - `boost` is added to the raw fp32 logit of every token that labels an edge out of the row's node or an edge out of
+ *     the root (once where it labels both), BEFORE SuppressBlank / SuppressTokens / ApplyTimestampRules, exactly like a
+ *     LogitFilter at the front of the list: a suppressed token stays suppressed, the timestamp-mass rule and the
+ *     log-probabilities that are accumulated see the biased logits;
+ *   - after token t is chosen the node becomes the child reached by t from the node, else the root's child reached by
+ *     t, else the root (so a timestamp, <|endoftext|> or any token outside the list returns to the root).
+ * Two limits: there are no failure links other than to the root (a phrase that starts in the middle of an abandoned
+ * one is only picked up from its first token), and a boost already given to a phrase that is then abandoned is not
+ * taken back.  The step logits the task holds are not modified; wh_task_step / wh_task_prefill ignore the list (their
+ * logits are raw).  The beam loop does not carry the nodes through its row permutation: wh_task_beam /
+ * wh_task_beam_begin return WH_ERR_STATE while a list is set. */
+#define WH_PHRASE_MAX_PHRASES 4096   /* per list; checked where the trie is built (whisper_amd.phrases) */
+#define WH_PHRASE_MAX_TOKENS 32      /* per phrase; likewise */
+#define WH_PHRASE_MAX_NODES 65535    /* root included */
+typedef struct wh_phrases {
+  int32_t n_nodes, n_edges;          /* n_edges == n_nodes - 1 */
+  const int32_t *child_begin;        /* device [n_nodes + 1] */
+  const int32_t *child_token;        /* device [n_edges] */
+  const int32_t *child_node;         /* device [n_edges] */
+  float boost;                       /* finite, non-zero; negative discourages the phrases */
+} wh_phrases;
+/* Stream-ordered (the call does not wait): the task derives the root's token -> child table into its own workspace and
+ * keeps the three pointers, which must stay valid until the list is cleared — by p == NULL here or by wh_task_reset.
+ * Applies to the loops begun after the call.  WH_ERR_ARG on a null task or pointer, n_nodes < 2 or > WH_PHRASE_MAX_NODES,
+ * n_edges != n_nodes - 1, a boost that is not finite or is 0; WH_ERR_STATE while a begun loop is pending — all before
+ * any device work. */
+int wh_task_set_phrases(wh_task *t, const wh_phrases *p, void *stream);
 /* number of cached self-attention positions of the longest row (the `offset` of model.py:234) */
 int wh_task_position(const wh_task *t);
 /* Introspection for tests and the benchmark.  what = 0: 1 when this task's decode step runs the cross attention with its

@@ -25,6 +25,7 @@ from .audio import log_mel_spectrogram, pad_or_trim
 from .decoding import (DecodingOptions, DecodingResult, ScoreResult, decode, decode_many, detect_language, run_in_lanes,
                        run_interleaved, score)
 from .model import ModelDimensions, Whisper
+from .phrases import PhraseList
 from .registry import ALIGNMENT_HEADS as _ALIGNMENT_HEADS
 from .registry import MODEL_URLS as _MODELS
 from .transcribe import plan_chunks, transcribe, transcribe_batch, transcribe_chunked

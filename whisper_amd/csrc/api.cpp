@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
@@ -300,7 +301,11 @@ struct wh_task {
   std::atomic<int> busy;   // handles are not thread-safe: a second thread entering while a call runs gets WH_ERR_STATE
   int64_t* step_tokens;
   float* samp_part;        // greedy sampler stage-1 partials
-  int* samp_state;         // [R][4] timestamp-rule state of the fused greedy loop
+  int* samp_state;         // [R][4] timestamp-rule state of the fused greedy loop; [3] = the row's phrase-trie node
+  // phrase list (wh_task_set_phrases): the caller's CSR trie + what the sampler derives from it, in the task's own memory
+  wh_phrases phrases; bool phrases_on;
+  int* phrase_root;        // [V] root child reached by every token, -1 = none
+  int* phrase_span;        // [R][2] child_begin pair of every row's node ({0, 0} at the root)
   void* beam_scratch;      // beam search partials / candidates (G > 1)
   int* beam_flags;         // [2][B] completion flags + [1] applied-update counter
   int* beam_lcp;           // [B][8][8] shared-history lengths of the rows of a segment + [R] first position to copy
@@ -330,6 +335,7 @@ struct wh_loop {
   int64_t* fin_tokens; int32_t* fin_len; float* fin_scores; int32_t* fin_count;
   // loop state
   SampleArgs sa; BeamArgs ba;
+  PhraseArgs ph; bool biased;        // the greedy sampler's phrase arguments, when the task had a list at the loop's start
   bool fused_embed, pending, wait_due;
   int ntok, steps, ntok_at_copy, cur;
   int n_tokens;                      // result
@@ -416,6 +422,8 @@ static void task_carve(wh_task* t, void* base) {
   t->step_tokens = (int64_t*)c.take(R * 8);
   t->samp_part = (float*)c.take(greedy_sample_scratch_bytes((int)R, (int)V));
   t->samp_state = (int*)c.take(R * 16);
+  t->phrase_root = (int*)c.take(V * 4);
+  t->phrase_span = (int*)c.take(R * 8);
   t->beam_scratch = t->G > 1 ? c.take(beam_scratch_bytes((int)R, (int)V)) : nullptr;
   t->beam_flags = t->G > 1 ? (int*)c.take((2 * (size_t)t->B + 1) * 4) : nullptr;
   t->beam_lcp = t->G > 1 ? (int*)c.take(((size_t)t->B * 64 + R) * 4) : nullptr;
@@ -545,6 +553,7 @@ static int task_reset_impl(wh_task* t, void* stream_) {
     memset(t->h_lag, 0, (size_t)t->R * sizeof(int));
     t->lag_on = false;
   }
+  t->phrases_on = false;                         // the sampler reads the derived tables only while a list is set
   t->needs_reset = false;
   return WH_OK;
 }
@@ -569,6 +578,24 @@ extern "C" int wh_task_set_lag(wh_task* t, const int32_t* lag, void* stream) {
   HIPCHK(hipMemcpyAsync(t->d_lag, t->h_lag, (size_t)t->R * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   t->lag_on = any;
+  return WH_OK;
+}
+
+// Phrase list for the device-side greedy / sampling loop (sampling.hip, BIAS): the caller's trie stays where it is, the
+// task derives the root's token -> child table into its own memory, stream-ordered.  NULL clears; so does wh_task_reset.
+extern "C" int wh_task_set_phrases(wh_task* t, const wh_phrases* p, void* stream) {
+  TASK_ENTER(t);
+  if (!t) return WH_ERR_ARG;
+  if (!p) { t->phrases_on = false; return WH_OK; }
+  if (!p->child_begin || !p->child_token || !p->child_node) return WH_ERR_ARG;
+  // a trie: every node but the root has exactly one edge into it
+  if (p->n_nodes < 2 || p->n_nodes > WH_PHRASE_MAX_NODES || p->n_edges != p->n_nodes - 1) return WH_ERR_ARG;
+  if (!std::isfinite(p->boost) || p->boost == 0.f) return WH_ERR_ARG;
+  if (t->needs_reset) { const int rc = task_reset_impl(t, stream); if (rc != WH_OK) return rc; }
+  HIPCHK(launch_phrase_root_table(p->child_begin, p->child_token, p->child_node, p->n_edges, t->m->d.n_vocab,
+                                  t->phrase_root, (hipStream_t)stream));
+  t->phrases = *p;
+  t->phrases_on = true;
   return WH_OK;
 }
 
@@ -1196,6 +1223,14 @@ static int greedy_start(wh_task* t) {
   sa.step_tokens = t->step_tokens; sa.d_alive_step = t->d_alive; sa.partials = t->samp_part;
   sa.row_state = t->samp_state;
   HIPCHK(hipMemsetAsync(t->samp_state, 0, (size_t)R * 16, s));
+  PhraseArgs& ph = L->ph; memset(&ph, 0, sizeof(ph));
+  L->biased = t->phrases_on;
+  if (L->biased) {                             // every row starts at the root, again after a hand-off fallback's re-run
+    ph.child_begin = t->phrases.child_begin; ph.child_token = t->phrases.child_token; ph.child_node = t->phrases.child_node;
+    ph.root_child = t->phrase_root; ph.span = t->phrase_span;
+    ph.n_nodes = t->phrases.n_nodes; ph.n_edges = t->phrases.n_edges; ph.boost = t->phrases.boost;
+    HIPCHK(hipMemsetAsync(t->phrase_span, 0, (size_t)R * 8, s));
+  }
   // the sampler also writes the next step's input row (token embedding + position): the step graph starts at layer 0
   L->fused_embed = !WH_DEV_FLAG("WH_NO_FUSED_EMBED");   // developer A/B switch
   if (L->fused_embed) {
@@ -1207,7 +1242,7 @@ static int greedy_start(wh_task* t) {
     sa.seed_lo = (uint32_t)(p->seed & 0xffffffffu); sa.seed_hi = (uint32_t)(p->seed >> 32);
   }
   sa.logits = t->logits + (size_t)(n_sel - 1) * V; sa.logits_ld = (int64_t)n_sel * V;
-  HIPCHK(launch_greedy_sample(sa, s));
+  HIPCHK(launch_greedy_sample(sa, s, L->biased ? &ph : nullptr));
   sa.logits = t->logits; sa.logits_ld = V;
   L->ntok = T0 + 1; L->steps = 1;
   L->pending = L->wait_due = false; L->ntok_at_copy = 0;
@@ -1340,7 +1375,7 @@ static int loop_pump(wh_task* t, bool block) {
         if (!(L->steps < p->max_steps && L->ntok <= p->n_ctx && L->ntok <= d.n_text_ctx)) break;
         int rc = step_run(t, s, t->loop_kind == LOOP_GREEDY && L->fused_embed);
         if (rc != WH_OK) return rc;
-        if (t->loop_kind == LOOP_GREEDY) HIPCHK(launch_greedy_sample(L->sa, s));
+        if (t->loop_kind == LOOP_GREEDY) HIPCHK(launch_greedy_sample(L->sa, s, L->biased ? &L->ph : nullptr));
         else { rc = beam_update(t, t->logits, d.n_vocab, 0); if (rc != WH_OK) return rc; }
         ++L->ntok; ++L->steps;
         if (L->pending && (L->steps & 7) == 2) L->wait_due = true;
@@ -1404,6 +1439,7 @@ static int beam_check(const wh_task* t, const wh_beam_params* bp, const int64_t*
                       const float* sum_logprobs, const int64_t* fin_tokens, const int32_t* fin_len, const float* fin_scores,
                       const int32_t* fin_count) {
   if (!t || !bp || !tokens || !sum_logprobs || !fin_tokens || !fin_len || !fin_scores || !fin_count) return WH_ERR_ARG;
+  if (t->phrases_on) return WH_ERR_STATE;      // the beam loop does not carry trie nodes through its row permutation
   const wh_greedy_params* p = &bp->rules;
   const wh_dims& d = t->m->d;
   const int R = t->R, G = t->G, T0 = p->sample_begin;

@@ -283,8 +283,28 @@ struct SampleArgs {
   // With it the partial kernel does not walk the row's sampled tokens (three dependent round trips per step).
   int* row_state;
 };
+// Phrase biasing inside the sampler (include/whisper_hip.h, wh_task_set_phrases): a token trie in CSR form, node 0 the root.
+// Row r's trie node lives in row_state[4 r + 3] (the slot the timestamp rules leave unused; row_state must then be given);
+// `span` holds the child_begin pair of that node, {0, 0} at the root, whose edges `root_child` already answers — kept per
+// row by the final kernel so that the partial kernel asks for it together with the logits instead of behind the state.
+// Both are zeroed before the first sample of a sequence.
+struct PhraseArgs {
+  const int* child_begin;     // [n_nodes + 1]
+  const int* child_token;     // [n_edges], ascending within a node
+  const int* child_node;      // [n_edges]
+  const int* root_child;      // [V]: the root's child reached by token v, or -1
+  int* span;                  // [R][2]
+  int n_nodes, n_edges;
+  float boost;
+};
 size_t greedy_sample_scratch_bytes(int R, int V);
-hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream);
+// ph == nullptr: the unbiased instantiations, which never look at the phrase arguments
+hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const PhraseArgs* ph = nullptr);
+// root[v] = child of the root reached by token v, else -1 (tokens outside [0, V) are ignored)
+hipError_t launch_phrase_root_table(const int* child_begin, const int* child_token, const int* child_node, int n_edges,
+                                    int V, int* root, hipStream_t stream);
+// span[r] = child_begin pair of the node in row_state[4 r + 3], {0, 0} for the root or a node outside [0, n_nodes)
+hipError_t launch_phrase_span(const int* row_state, const int* child_begin, int n_nodes, int R, int* span, hipStream_t stream);
 hipError_t launch_no_speech(const float* logits_row0, int64_t row_stride, int R, int V, int no_speech,
                             float* out, hipStream_t stream);
 // dst[r] = src[r*stride]

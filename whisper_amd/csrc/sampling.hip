@@ -8,6 +8,8 @@
 // "timestamp probability mass > best text token" rule (:498-505) and the final normaliser follow
 // without re-reading the row.  The row's token history (needed by the pairing / monotonicity rules)
 // is scanned in parallel.
+#include <string.h>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -80,9 +82,16 @@ constexpr int PSTRIDE = 8;      // floats per (row, chunk, range) partial: m, s,
 // Stage 1: grid (chunks, rows).  Applies the filters to one 1024-entry slice of the row and reduces it
 // to two partial statistics (text range, timestamp range): {max, sum exp(x - max), first arg-max}.
 // All four logits of a thread are requested before any is used (one L2 round trip per workgroup).
-template <bool SAMPLE>
-__global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, int nchunk) {
+// BIAS (phrase lists, kernels.h PhraseArgs): `boost` is added to the logit of every token that labels an edge out of the
+// row's trie node or out of the root, BEFORE the filters — a LogitFilter at the front of the list; the logits buffer itself
+// is left alone.  Root membership is one more coalesced load at the logits' own indices; the node's child_begin pair sits in
+// `span` (left by the previous step's final kernel) and is asked for in the same batch.  Only the node's child tokens come
+// one round trip later: 64 per wave in one coalesced load, of which those inside this workgroup's 1024-entry slice (usually
+// none: the children of a node fall into few of the ~50 slices) are handed round as wave-uniform values.
+template <bool SAMPLE, bool BIAS>
+__global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, int nchunk, whk::PhraseArgs ph) {
   pin_kernargs(a);
+  if constexpr (BIAS) pin_kernargs(ph);
   asm volatile("" ::"s"(nchunk));
   __shared__ int sh_last_ts;
   __shared__ float sh_m[2][4], sh_s[2][4];
@@ -96,6 +105,15 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
   for (int j = 0; j < 4; ++j) {
     const int v = c * SCHUNK + j * 256 + tid;
     xv[j] = v < a.V ? x[v] : WH_NEG_INF;
+  }
+  int rootc[4] = {-1, -1, -1, -1}, vsb = 0, vse = 0;
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int v = c * SCHUNK + j * 256 + tid;
+      if (v < a.V) rootc[j] = ph.root_child[v];
+    }
+    vsb = load_agent_int(ph.span + 2 * k); vse = load_agent_int(ph.span + 2 * k + 1);
   }
   const int vl = load_agent_int(a.lag ? a.lag + k : a.d_ntok), vn = load_agent_int(a.d_ntok);
   const int lag = a.lag ? uniform(vl) : 0;   // ragged prompts: this row's indices sit lag earlier than the longest row's
@@ -132,6 +150,28 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
   }
   const int split = ts_rules ? TB : a.V;   // text range [0, split), timestamp range [split, V)
 
+  bool hit[4] = {false, false, false, false};
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hit[j] = rootc[j] >= 0;
+    int sb = uniform(vsb), se = uniform(vse);
+    if (L == 0 || sb < 0) sb = se = 0;       // a row's first sampled token is decided at the root
+    if (se > ph.n_edges) se = ph.n_edges;
+    const int lo = c * SCHUNK;
+    for (int e0 = sb; e0 < se; e0 += 64) {
+      const int e = e0 + lane;
+      const int tk = e < se ? ph.child_token[e] : -1;
+      unsigned long long m = __ballot((unsigned)(tk - lo) < (unsigned)SCHUNK);
+      while (m) {                             // wave-uniform: the lanes whose child token lies in this slice
+        const int i = __builtin_ctzll(m);
+        m &= m - 1;
+        const int d = __builtin_amdgcn_readlane(tk, i) - lo - tid;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hit[j] = hit[j] || d == j * 256;
+      }
+    }
+  }
+
   Stat st[2];
   st[0] = Stat{WH_NEG_INF, 0.f, 0x7fffffff};
   st[1] = Stat{WH_NEG_INF, 0.f, 0x7fffffff};
@@ -158,11 +198,13 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
       }
     }
     if (masked) continue;
-    if (v < split) stat_add(st[0], xv[j], v); else stat_add(st[1], xv[j], v);
+    float xj = xv[j];
+    if constexpr (BIAS) { if (hit[j]) xj += ph.boost; }
+    if (v < split) stat_add(st[0], xj, v); else stat_add(st[1], xj, v);
     if constexpr (SAMPLE) {
-      if (xv[j] != WH_NEG_INF) {
-        const float key = xv[j] * a.inv_temperature + gumbel(a.seed_lo, a.seed_hi, step, k, v);
-        pick_merge(pk[v < split ? 0 : 1], key, xv[j], v);
+      if (xj != WH_NEG_INF) {
+        const float key = xj * a.inv_temperature + gumbel(a.seed_lo, a.seed_hi, step, k, v);
+        pick_merge(pk[v < split ? 0 : 1], key, xj, v);
       }
     }
   }
@@ -196,16 +238,24 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
 
 // Stage 2: one workgroup per row merges the chunk partials, applies the "timestamp mass" rule and
 // GreedyDecoder.update, and appends the token.
-template <bool SAMPLE>
-__global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, int nchunk) {
+// BIAS: the row's trie node then follows the token — the edge out of the node, else the edge out of the root, else the
+// root.  The whole workgroup finds it in one round trip that starts as soon as the token is known and runs beside the
+// embedding gather: thread i asks for child i of the node (token and target), thread 0 for root_child[token]; a loop only
+// for a node of more than 256 children.  Thread 0 stores the node (row_state slot 3) and its child_begin pair (`span`).
+template <bool SAMPLE, bool BIAS>
+__global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, int nchunk, whk::PhraseArgs ph) {
   pin_kernargs(a);
+  if constexpr (BIAS) pin_kernargs(ph);
   asm volatile("" ::"s"(nchunk));
   __shared__ float sh_m[2][4], sh_s[2][4];
   __shared__ int sh_i[2][4];
   __shared__ float sh_k[2][4], sh_x[2][4];
   __shared__ int sh_next;
+  __shared__ int sh_child;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int k = blockIdx.x;
+  int vsb = 0, vse = 0;
+  if constexpr (BIAS) { vsb = load_agent_int(ph.span + 2 * k); vse = load_agent_int(ph.span + 2 * k + 1); }
   const int vl = load_agent_int(a.lag ? a.lag + k : a.d_ntok), vn = load_agent_int(a.d_ntok);
   const int lag = a.lag ? uniform(vl) : 0;
   const int ntok = uniform(vn) - lag;
@@ -238,6 +288,7 @@ __global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, in
       if constexpr (SAMPLE) { sh_k[g][wave] = pk[g].key; sh_x[g][wave] = pk[g].x; }
     }
   }
+  if constexpr (BIAS) { if (tid == 0) sh_child = -1; }
   __syncthreads();
   if (tid == 0) {
     const int64_t last_tok = row[ntok - 1];
@@ -290,8 +341,18 @@ __global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, in
       if (is_ts) st[2] = next + 1;
     }
   }
-  if (a.x_next) {                             // the next step's input row: embedding of the token just chosen, at its index
+  int sb = 0, se = 0, nxt = 0, tk0 = -1, cn0 = 0, rootc = -1;
+  if constexpr (BIAS) {
     __syncthreads();
+    nxt = sh_next;
+    sb = uniform(vsb); se = uniform(vse);
+    if (ntok == a.sample_begin - lag || sb < 0) sb = se = 0;     // a row's first sampled token leaves from the root
+    if (se > ph.n_edges) se = ph.n_edges;
+    if (sb + tid < se) { tk0 = ph.child_token[sb + tid]; cn0 = ph.child_node[sb + tid]; }
+    if (tid == 0 && nxt >= 0 && nxt < a.V) rootc = ph.root_child[nxt];
+  }
+  if (a.x_next) {                             // the next step's input row: embedding of the token just chosen, at its index
+    if constexpr (!BIAS) __syncthreads();
     int tok = sh_next;
     if (tok < 0) tok = 0;
     if (tok > a.V - 1) tok = a.V - 1;
@@ -307,6 +368,42 @@ __global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, in
       }
     }
   }
+  if constexpr (BIAS) {
+    if (tk0 == nxt) sh_child = cn0;           // child tokens are distinct within a node: at most one writer
+    for (int e = sb + 256 + tid; e < se; e += 256)
+      if (ph.child_token[e] == nxt) sh_child = ph.child_node[e];
+    __syncthreads();
+    if (tid == 0) {
+      int ns = sh_child >= 0 ? sh_child : (rootc >= 0 ? rootc : 0);
+      if (ns >= ph.n_nodes) ns = 0;
+      int b = 0, e = 0;
+      if (ns > 0) { b = ph.child_begin[ns]; e = ph.child_begin[ns + 1]; }
+      a.row_state[4 * k + 3] = ns;
+      ph.span[2 * k] = b; ph.span[2 * k + 1] = e;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void phrase_root_table_kernel(const int* __restrict__ child_begin, const int* __restrict__ child_token,
+                                                                const int* __restrict__ child_node, int n_edges, int V,
+                                                                int* __restrict__ root) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  int end = child_begin[1];
+  if (end > n_edges) end = n_edges;
+  if (e < end) {
+    const int t = child_token[e];
+    if (t >= 0 && t < V) root[t] = child_node[e];
+  }
+}
+
+__global__ void phrase_span_kernel(const int* __restrict__ row_state, const int* __restrict__ child_begin, int n_nodes, int R,
+                                   int* __restrict__ span) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const int s = row_state[4 * r + 3];
+  const bool inner = s > 0 && s < n_nodes;
+  span[2 * r] = inner ? child_begin[s] : 0;
+  span[2 * r + 1] = inner ? child_begin[s + 1] : 0;
 }
 
 // softmax(logits at <|startoftranscript|>)[no_speech] per row (decoding.py:689-693).  One workgroup of 1024 threads per
@@ -363,16 +460,44 @@ namespace whk {
 
 size_t greedy_sample_scratch_bytes(int R, int V) { return (size_t)R * ((V + SCHUNK - 1) / SCHUNK) * 2 * PSTRIDE * sizeof(float); }
 
-hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream) {
+template <bool SAMPLE, bool BIAS>
+static void greedy_sample_launch(const SampleArgs& a, const PhraseArgs& ph, int nchunk, hipStream_t stream) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS>), dim3(nchunk, a.R), dim3(256), 0, stream, a, nchunk, ph);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_final_kernel<SAMPLE, BIAS>), dim3(a.R), dim3(256), 0, stream, a, nchunk, ph);
+}
+
+hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const PhraseArgs* ph) {
   const int nchunk = (a.V + SCHUNK - 1) / SCHUNK;
   if (!a.partials) return hipErrorInvalidValue;
-  if (a.inv_temperature > 0.f) {
-    hipLaunchKernelGGL(greedy_partial_kernel<true>, dim3(nchunk, a.R), dim3(256), 0, stream, a, nchunk);
-    hipLaunchKernelGGL(greedy_final_kernel<true>, dim3(a.R), dim3(256), 0, stream, a, nchunk);
+  const bool sample = a.inv_temperature > 0.f;
+  if (ph) {
+    if (!ph->child_begin || !ph->child_token || !ph->child_node || !ph->root_child || !ph->span || !a.row_state ||
+        ph->n_nodes < 1 || ph->n_edges < 0)
+      return hipErrorInvalidValue;
+    if (sample) greedy_sample_launch<true, true>(a, *ph, nchunk, stream);
+    else greedy_sample_launch<false, true>(a, *ph, nchunk, stream);
   } else {
-    hipLaunchKernelGGL(greedy_partial_kernel<false>, dim3(nchunk, a.R), dim3(256), 0, stream, a, nchunk);
-    hipLaunchKernelGGL(greedy_final_kernel<false>, dim3(a.R), dim3(256), 0, stream, a, nchunk);
+    PhraseArgs none;
+    memset(&none, 0, sizeof(none));
+    if (sample) greedy_sample_launch<true, false>(a, none, nchunk, stream);
+    else greedy_sample_launch<false, false>(a, none, nchunk, stream);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_phrase_root_table(const int* child_begin, const int* child_token, const int* child_node, int n_edges,
+                                    int V, int* root, hipStream_t stream) {
+  if (!child_begin || !child_token || !child_node || !root || n_edges < 1 || V < 1) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(root, 0xff, (size_t)V * 4, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(phrase_root_table_kernel, dim3((n_edges + 255) / 256), dim3(256), 0, stream, child_begin, child_token,
+                     child_node, n_edges, V, root);
+  return hipGetLastError();
+}
+
+hipError_t launch_phrase_span(const int* row_state, const int* child_begin, int n_nodes, int R, int* span, hipStream_t stream) {
+  if (!row_state || !child_begin || !span || n_nodes < 1 || R < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(phrase_span_kernel, dim3((R + 63) / 64), dim3(64), 0, stream, row_state, child_begin, n_nodes, R, span);
   return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@ from torch.distributions import Categorical
 
 from . import hip
 from .audio import CHUNK_LENGTH
+from .phrases import PhraseList, as_phrase_list
 from .tokenizer import Tokenizer, get_tokenizer
 from .utils import compression_ratio
 
@@ -454,6 +455,39 @@ class ApplyTimestampRules(LogitFilter):
         logits[:, :TB] = logits[:, :TB].masked_fill((ts_mass > best_text)[:, None], -np.inf)
 
 
+class PhraseBias(LogitFilter):
+    """A phrase list (phrases.py) as a logit filter: adds the list's boost to every token that continues a listed phrase
+    from the row's trie state or starts one.  Stateless — every call recomputes a row's state by walking its sampled tokens
+    `tokens[row, sample_begin:]` — so beam search's row permutation needs no hook.  It goes FIRST in `logit_filters`.  This
+    is the host-loop form; the device-side greedy / sampling loop applies the same rule inside its sampler
+    (csrc/sampling.hip) and keeps the state per row instead of re-walking.
+    `row_begin`: per-row `sample_begin` for rows whose prompts differ in length (row r's sampled tokens are then
+    `tokens[r, row_begin[r]:]`)."""
+
+    def __init__(self, phrases: PhraseList, sample_begin: int, row_begin: Optional[Sequence[int]] = None):
+        self.phrases = phrases
+        self.sample_begin = sample_begin
+        self.row_begin = list(row_begin) if row_begin is not None else None
+
+    def apply(self, logits: Tensor, tokens: Tensor):
+        ph = self.phrases
+        rows = tokens.tolist()
+        if self.row_begin is not None and len(self.row_begin) != len(rows):
+            raise ValueError(f"{len(self.row_begin)} sample_begin values for {len(rows)} rows")
+        root = ph.children[0]
+        idx_r, idx_c = [], []
+        for r, row in enumerate(rows):
+            begin = self.row_begin[r] if self.row_begin is not None else self.sample_begin
+            state = ph.walk(row[begin:])
+            if state:
+                extra = [t for t in ph.children[state] if t not in root]       # a token of both sets is boosted once
+                idx_r.extend([r] * len(extra))
+                idx_c.extend(extra)
+        logits[:, ph.root_tokens(logits.device)] += ph.boost
+        if idx_r:
+            logits[torch.tensor(idx_r, device=logits.device), torch.tensor(idx_c, device=logits.device)] += ph.boost
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # the task
 # ---------------------------------------------------------------------------------------------------------------
@@ -466,8 +500,13 @@ class DecodingTask:
     decoder: TokenDecoder
     logit_filters: List[LogitFilter]
 
-    def __init__(self, model: "Whisper", options: DecodingOptions, prompts: Optional[Sequence[Sequence[int]]] = None):
-        """`prompts` (no counterpart in the reference, whose task shares ONE initial_tokens tuple between all rows,
+    def __init__(self, model: "Whisper", options: DecodingOptions, prompts: Optional[Sequence[Sequence[int]]] = None,
+                 phrases: Optional[Union[PhraseList, Sequence]] = None):
+        """`phrases` (no counterpart in the reference; it travels as a keyword because DecodingOptions keeps the reference's
+        fields): a `PhraseList`, or a plain list of strings / token-id lists compiled at the default boost — phrases the
+        decoder should prefer (phrases.py).  Greedy decoding and sampling apply it inside the device-side loop; beam search
+        runs the host loop with the `PhraseBias` filter.
+        `prompts` (no counterpart in the reference, whose task shares ONE initial_tokens tuple between all rows,
         decoding.py:719): one previous-text token list per audio segment, each used exactly as
         `options.prompt` would be for that segment alone.  Prompts of different lengths ("ragged") are decoded by the
         device-side loops (greedy, sampling, beam search: wh_task_set_lag), every row at its own positions;
@@ -521,6 +560,13 @@ class DecodingTask:
             if options.max_initial_timestamp:
                 self._max_initial_ts = round(self.options.max_initial_timestamp / precision)
             self.logit_filters.append(ApplyTimestampRules(tokenizer, self.sample_begin, self._max_initial_ts))
+        self.phrases: Optional[PhraseList] = as_phrase_list(phrases, tokenizer)
+        if self.phrases is not None:
+            self.phrases.check_vocabulary(tokenizer.eot)
+            row_begin = None
+            if self.row_lag is not None and any(self.row_lag):
+                row_begin = [self.sample_begin - lag for lag in self.row_lag for _ in range(self.n_group)]
+            self.logit_filters.insert(0, PhraseBias(self.phrases, self.sample_begin, row_begin))
         self._stock_filters = list(self.logit_filters)
 
     def _verify_options(self, options: DecodingOptions) -> DecodingOptions:
@@ -601,7 +647,7 @@ class DecodingTask:
         return (type(self.decoder) is GreedyDecoder and self.options.temperature >= 0
                 and (self.n_group == 1 or self.options.temperature > 0)
                 and type(self.inference) is HipInference and self.logit_filters == self._stock_filters
-                and all(type(f) in (SuppressBlank, SuppressTokens, ApplyTimestampRules) for f in self.logit_filters)
+                and all(type(f) in (PhraseBias, SuppressBlank, SuppressTokens, ApplyTimestampRules) for f in self.logit_filters)
                 and self.sample_begin + self.sample_len <= 2 * self.n_ctx)
 
     def _beam_shape_ok(self) -> bool:
@@ -707,6 +753,8 @@ class DecodingTask:
             row_lag = [lag for lag in self.row_lag for _ in range(self.n_group)] if ragged else None
             if ragged:
                 task.set_lag(row_lag)
+            if self.phrases is not None:         # PhraseBias, inside the sampler (the task forgets the list when it is reset)
+                task.set_phrases(self.phrases.device_arrays(dev), self.phrases.boost)
             if wait:
                 res = task.greedy(buf, params, self.sot_index, no_speech)
             else:
@@ -885,13 +933,16 @@ class DecodingTask:
 def decode(model: "Whisper", mel: Tensor, options: DecodingOptions = DecodingOptions(),
            prompts: Optional[Sequence[Sequence[int]]] = None, **kwargs) -> Union[DecodingResult, List[DecodingResult]]:
     """Decode 30-second segment(s) given as (n_mels, 3000) or (*, n_mels, 3000) log-mel spectrograms.
-    `prompts`: optional previous-text token list per segment (see DecodingTask)."""
+    `prompts`: optional previous-text token list per segment (see DecodingTask).  `phrases=` among the keywords (the
+    parameter list stays the reference's plus `prompts`): a phrase list to prefer, a `PhraseList` or a plain list of strings
+    (see DecodingTask); the other keywords replace fields of `options`."""
+    phrases = kwargs.pop("phrases", None)
     single = mel.ndim == 2
     if single:
         mel = mel.unsqueeze(0)
     if kwargs:
         options = replace(options, **kwargs)
-    result = DecodingTask(model, options, prompts).run(mel)
+    result = DecodingTask(model, options, prompts, phrases).run(mel)
     return result[0] if single else result
 
 
@@ -1172,7 +1223,8 @@ def coalesce_batches(rows: Sequence[int], chain_rows: Optional[int]) -> List[Lis
 
 
 def decode_many(model: "Whisper", mels: Sequence[Tensor], options: DecodingOptions = DecodingOptions(), in_flight: int = 3,
-                chain_rows: Optional[int] = 24, **kwargs) -> List[List[DecodingResult]]:
+                chain_rows: Optional[int] = 24, phrases: Optional[Union[PhraseList, Sequence]] = None,
+                **kwargs) -> List[List[DecodingResult]]:
     """`decode(model, mel, options)` for every batch of `mels` — each a (B, n_mels, 3000) tensor, or raw (B, 480000) audio (its
     log-mel is then taken here, per batch: audio.py:155 clamps against the maximum over the tensor it is given) — scheduled for
     throughput; returns the per-batch result lists in order.  No counterpart in the reference.  Two levers:
@@ -1185,9 +1237,12 @@ def decode_many(model: "Whisper", mels: Sequence[Tensor], options: DecodingOptio
         tie to within rounding.  None / 0: every batch is its own chain.
       * `in_flight`: up to this many chains are decoded at once, each on a HIP stream of its own, all driven from the calling
         thread (`run_interleaved`): chains of few rows leave the chip idle between their dependent launches and fill each other's
-        gaps.  Chains of 16+ rows of a large model gain little from it."""
+        gaps.  Chains of 16+ rows of a large model gain little from it.
+    `phrases`: one phrase list for all batches (see DecodingTask)."""
     if kwargs:
         options = replace(options, **kwargs)
+    if phrases is not None and not isinstance(phrases, PhraseList):      # compiled once, shared by every chain
+        phrases = as_phrase_list(phrases, get_tokenizer(model.is_multilingual, num_languages=model.num_languages))
     dtype = torch.float16 if options.fp16 else torch.float32
     mels = list(mels)
     group = options.beam_size or options.best_of or 1
@@ -1208,7 +1263,7 @@ def decode_many(model: "Whisper", mels: Sequence[Tensor], options: DecodingOptio
                 from .audio import log_mel_spectrogram
                 x = log_mel_spectrogram(x, model.dims.n_mels)
             parts.append(x.to(dtype))
-        res = yield from DecodingTask(model, options).run_steps(parts[0] if len(parts) == 1 else torch.cat(parts), wait=False)
+        res = yield from DecodingTask(model, options, phrases=phrases).run_steps(parts[0] if len(parts) == 1 else torch.cat(parts), wait=False)
         out, at = [], 0
         for p_ in parts:
             out.append(res[at: at + p_.shape[0]])

@@ -83,6 +83,15 @@ class GreedyParams(C.Structure):
     ]
 
 
+class Phrases(C.Structure):
+    """wh_phrases: a token trie in CSR form (device int32 arrays) and its boost"""
+    _fields_ = [
+        ("n_nodes", C.c_int32), ("n_edges", C.c_int32),
+        ("child_begin", C.c_void_p), ("child_token", C.c_void_p), ("child_node", C.c_void_p),
+        ("boost", C.c_float),
+    ]
+
+
 class BeamParams(C.Structure):
     _fields_ = [("rules", GreedyParams), ("beam_size", C.c_int32), ("max_candidates", C.c_int32)]
 
@@ -112,6 +121,7 @@ SIGNATURES = {
     "wh_task_rearrange": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "wh_task_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "wh_task_set_lag": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "wh_task_set_phrases": (C.c_int, [C.c_void_p, C.POINTER(Phrases), C.c_void_p]),
     "wh_task_position": (C.c_int, [C.c_void_p]),
     "wh_task_info": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "wh_task_greedy": (C.c_int, [C.c_void_p, C.POINTER(GreedyParams), C.c_void_p, C.c_int64, C.c_int, C.c_int,
@@ -752,6 +762,28 @@ class HipTask:
     def reset(self):
         with self._call():
             check(lib().wh_task_reset(self.handle, stream_ptr(self.stream)), "wh_task_reset")
+        self._phrase_arrays = None
+
+    def set_phrases(self, arrays: Optional[Sequence[torch.Tensor]], boost: float = 0.0):
+        """phrase list of the device-side greedy / sampling loop (wh_task_set_phrases): `arrays` = the trie's CSR arrays
+        (child_begin, child_token, child_node: contiguous int32 tensors on the task's device), None clears.  The task keeps
+        the tensors alive until the list is cleared (`reset` clears it too)."""
+        if arrays is None:
+            with self._call():
+                check(lib().wh_task_set_phrases(self.handle, None, stream_ptr(self.stream)), "wh_task_set_phrases")
+            self._phrase_arrays = None
+            return
+        begin, token, node = arrays
+        for a in (begin, token, node):
+            assert a.is_cuda and a.dtype == torch.int32 and a.is_contiguous()
+        assert begin.numel() >= 2 and token.numel() == node.numel()
+        p = Phrases(n_nodes=begin.numel() - 1, n_edges=token.numel(), child_begin=begin.data_ptr(),
+                    child_token=token.data_ptr(), child_node=node.data_ptr(), boost=float(boost))
+        with self._call():
+            check(lib().wh_task_set_phrases(self.handle, C.byref(p), stream_ptr(self.stream)), "wh_task_set_phrases")
+        for a in (begin, token, node):
+            a.record_stream(self.stream)
+        self._phrase_arrays = (begin, token, node)
 
     def set_lag(self, lag: Optional[Sequence[int]]):
         """ragged prompts: row r's sequence is the longest row's shifted left by lag[r] (include/whisper_hip.h)"""

@@ -68,6 +68,29 @@ class _AlignRequest:
         self.audio_features = audio_features       # encoder output of this window from the decode (no second pass)
 
 
+def _pop_phrases(model: "Whisper", options: dict):
+    """take `phrases` / `phrase_boost` out of a keyword dict (the rest are DecodingOptions fields); a plain list is compiled
+    (phrases.PhraseList).  Returns what `decode(..., phrases=)` takes, or None."""
+    phrases, boost = options.pop("phrases", None), options.pop("phrase_boost", None)
+    if phrases is None and boost is None:
+        return None
+    from .phrases import as_phrase_list
+    return as_phrase_list(phrases, get_tokenizer(model.is_multilingual, num_languages=model.num_languages), boost)
+
+
+def _phrases_kw(phrases) -> dict:
+    """the keyword for `model.decode`: absent without a list, so that the call is the one made before phrase lists existed
+    (a caller's own model object need not know the keyword)"""
+    return {} if phrases is None else {"phrases": phrases}
+
+
+def _compile_phrases(model: "Whisper", kwargs: dict) -> None:
+    """replace a plain `phrases` list among the keywords by its PhraseList, once for all the files / chunks of a call"""
+    compiled = _pop_phrases(model, kwargs)
+    if compiled is not None:
+        kwargs["phrases"] = compiled
+
+
 class _Transcriber:
     def __init__(self, model: "Whisper", verbose, temperature, compression_ratio_threshold, logprob_threshold,
                  no_speech_threshold, condition_on_previous_text, initial_prompt, carry_initial_prompt,
@@ -85,6 +108,9 @@ class _Transcriber:
         self.prepend_punctuations = prepend_punctuations
         self.append_punctuations = append_punctuations
         self.hallucination_silence_threshold = hallucination_silence_threshold
+        # a phrase list is no DecodingOptions field (those stay the reference's): it leaves the keywords here and goes to
+        # every decode of this file — every window, every rung of the temperature ladder — as `phrases=`
+        self.phrases = _pop_phrases(model, decode_options)
         self.decode_options = decode_options
         self.initial_prompt = initial_prompt
         self.clip_timestamps = clip_timestamps
@@ -95,7 +121,7 @@ class _Transcriber:
         (reference transcribe.py:184-224); `first` skips temperatures already tried by a batched pass"""
         result = None
         for t in self.temperatures[first:]:
-            result = self.model.decode(segment, self._options_for(t))
+            result = self.model.decode(segment, self._options_for(t), **_phrases_kw(self.phrases))
             if not self._needs_retry(result):
                 break
             feats = getattr(result, "audio_features", None)
@@ -395,6 +421,9 @@ def transcribe(
     `device_ingest: bool = False` (no counterpart in the reference, so it travels among the keywords and the parameter list
     stays the reference's): a file path is loaded with `audio.load_audio(path, device=model.device)` — WAV / FLAC are
     down-mixed, resampled and quantised on the GPU; arrays and tensors are untouched.
+    `phrases` / `phrase_boost` (likewise among the keywords): phrases the decoder should prefer — a `phrases.PhraseList`, or a
+    list of strings compiled with `phrase_boost` (default 3.0 logit units); applied to every window and every rung of the
+    temperature ladder (phrases.py; inside the device-side loop for greedy decoding and sampling).
     """
     if decode_options.pop("device_ingest", False) and isinstance(audio, str):
         audio = load_audio(audio, device=model.device)
@@ -427,12 +456,12 @@ def _options_key(opts: dict):
 
 
 def _prompt_batches(model: "Whisper", options: DecodingOptions, prompts: List[Optional[List[int]]], members: List[int],
-                    batch_size: int) -> List[List[int]]:
+                    batch_size: int, phrases=None) -> List[List[int]]:
     """split `members` (windows with the same options and the prompts `prompts[i]`) into batches one DecodingTask
     can take: rows whose initial sequences have different lengths may share a call in the device-side modes (greedy,
     sampling, beam search with the stock decoder / filters) below the length limit (DecodingTask.ragged_limit: no row
     may reach the context limit before the step budget ends); any rows of EQUAL length may always share one"""
-    probe = DecodingTask(model, options)
+    probe = DecodingTask(model, options, phrases=phrases)       # (beam search with a phrase list runs the host loop: no ragged rows)
     limit = probe.ragged_limit()
     classes = {}
     for i in members:
@@ -497,8 +526,10 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
     a larger `batch_size` (rows per decode chain, up to 24) over more groups when there are enough files: a wider chain streams
     the decoder's weights once for all its rows.  Worth it from about 2 * batch_size files on.
     `device_ingest`: file paths are loaded as `load_audio(path, device=model.device)` loads them (WAV / FLAC down-mixed,
-    resampled and quantised on the GPU); the host-side parsing / FLAC decoding stays on the loader threads."""
+    resampled and quantised on the GPU); the host-side parsing / FLAC decoding stays on the loader threads.
+    `phrases` / `phrase_boost`: as in `transcribe`; one phrase list for all files."""
     audios = list(audios)
+    _compile_phrases(model, kwargs)              # `phrases` / `phrase_boost`: as in `transcribe`, one list for all files
     if in_flight > 1 and len(audios) > 1:
         from .decoding import run_in_lanes
         n = min(int(in_flight), len(audios))
@@ -619,20 +650,22 @@ def _drive_lockstep(model: "Whisper", workers: List[_Transcriber], start, batch_
             groups = {}
             for i in todo:
                 t = workers[i].temperatures[rung[i]]
-                groups.setdefault((_options_key(workers[i].decode_options), t), []).append(i)
+                groups.setdefault((_options_key(workers[i].decode_options), id(workers[i].phrases), t), []).append(i)
             todo = []
-            for (_, t), members in groups.items():
+            for (_, _, t), members in groups.items():
                 shared = replace(workers[members[0]]._options_for(t), prompt=None)
+                phrases = workers[members[0]].phrases
                 prompts = {i: workers[i].decode_options.get("prompt") for i in members}
-                for chunk in _prompt_batches(model, shared, prompts, members, batch_size):
+                for chunk in _prompt_batches(model, shared, prompts, members, batch_size, phrases):
                     # a window on a higher rung has been encoded already: its retry takes the features
                     inputs = [encoded.get(i, pending[i]) for i in chunk]
                     if len({tuple(x.shape) for x in inputs}) > 1:
                         inputs = [pending[i] for i in chunk]
                     if len(chunk) == 1:        # alone: exactly the call `transcribe` makes
-                        decoded = [model.decode(inputs[0], workers[chunk[0]]._options_for(t))]
+                        decoded = [model.decode(inputs[0], workers[chunk[0]]._options_for(t), **_phrases_kw(phrases))]
                     else:
-                        decoded = model.decode(torch.stack(inputs), shared, prompts=[prompts[i] for i in chunk])
+                        decoded = model.decode(torch.stack(inputs), shared, prompts=[prompts[i] for i in chunk],
+                                               **_phrases_kw(phrases))
                     for i, result in zip(chunk, decoded):
                         if workers[i]._needs_retry(result) and rung[i] + 1 < len(workers[i].temperatures):
                             rung[i] += 1
@@ -697,7 +730,8 @@ def transcribe_chunked(model: "Whisper", audio: Union[str, np.ndarray, torch.Ten
       * `clip_timestamps` cannot be combined with chunking (ValueError), nor can `min_chunk_s` outside (0, 30] or `guard_s`
         above 0.64 (the cut kernel's halo);
       * `verbose=True` prints the segments chunk by chunk in completion order, not in file order; there is no progress bar.
-    `device_ingest`: a file path is loaded with `load_audio(path, device=model.device)`, as in `transcribe`.
+    `device_ingest`: a file path is loaded with `load_audio(path, device=model.device)`, as in `transcribe`; `phrases` /
+    `phrase_boost` likewise.
 
     Returns the dict `transcribe` returns — `segments` concatenated in chunk order with `id` renumbered, `text` the
     concatenation of the chunks' texts, `language` — plus `chunks`: `[(start_s, end_s), ...]`.  A file of at most 30 s has no
@@ -708,6 +742,7 @@ def transcribe_chunked(model: "Whisper", audio: Union[str, np.ndarray, torch.Ten
     if batch_size < 1:
         raise ValueError(f"batch_size must be at least 1 (got {batch_size})")
     fixed = {k: kwargs.pop(k, default) for k, default in _WALK_DEFAULTS.items()}
+    _compile_phrases(model, kwargs)              # `phrases` / `phrase_boost`: as in `transcribe`, one list for all chunks
     if device_ingest and isinstance(audio, str):
         audio = load_audio(audio, device=model.device)
     mel = log_mel_spectrogram(audio, model.dims.n_mels, padding=N_SAMPLES, device=model.device)
