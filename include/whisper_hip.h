@@ -294,6 +294,29 @@ typedef struct wh_phrases {
  * n_edges != n_nodes - 1, a boost that is not finite or is 0; WH_ERR_STATE while a begun loop is pending — all before
  * any device work. */
 int wh_task_set_phrases(wh_task *t, const wh_phrases *p, void *stream);
+/* Repetition control inside wh_task_greedy / wh_task_greedy_begin (arg-max and sampling), the `no_repeat_ngram_size` and
+ * `repetition_penalty` of other Whisper runtimes; no counterpart in the reference, whose only answer to a decode that
+ * loops on a phrase is the temperature ladder.  For row r at a step, H is the row's SAMPLED tokens in order: the columns
+ * from the row's own sample_begin (sample_begin - lag[r]) to its current length, timestamps included; the
+ * start-of-transcript sequence, the prompt and a prefix are not part of H (text of the previous window stays
+ * repeatable).  L = |H|.
+ *   - repetition_penalty p != 1: for every token v < eot that occurs in H — as a SET, a token seen five times is
+ *     penalised once — the raw fp32 logit x[v] becomes x[v] / p if x[v] > 0 and x[v] * p if x[v] < 0; 0 and -inf stay.
+ *   - no_repeat_ngram_size n >= 1: if L >= n - 1, let s be the last n - 1 tokens of H (empty for n = 1); every token
+ *     H[i + n - 1] < eot with 0 <= i <= L - n and H[i .. i + n - 2] == s becomes -inf.  Timestamps and specials take
+ *     part in the contexts but ids >= eot are never banned: <|endoftext|> stays available and the timestamp rules
+ *     are never left with an empty row.
+ * Order: penalty (on the raw logit) -> phrase boost -> ban -> SuppressBlank -> SuppressTokens -> ApplyTimestampRules;
+ * the timestamp-mass rule, the arg-max / the draw and the accumulated log-probabilities see the edited logits.  A row
+ * that has reached <|endoftext|> stays there and accumulates nothing.  The step logits the task holds are not modified;
+ * wh_task_step / wh_task_prefill / wh_task_score ignore the setting.  Nothing is stored on the device: the sampler reads
+ * the row's own tokens at every step.  The beam loop does not apply it: wh_task_beam / wh_task_beam_begin return
+ * WH_ERR_STATE while it is set.
+ * Stream-ordered (the call does not wait); applies to the loops begun after the call; (0, 1.0f) clears it, and so does
+ * wh_task_reset.  WH_ERR_ARG on a null task, n < 0 or n > WH_REPETITION_MAX_NGRAM, a penalty that is not finite or is
+ * <= 0; WH_ERR_STATE while a begun loop is pending — all before any device work. */
+#define WH_REPETITION_MAX_NGRAM 16
+int wh_task_set_repetition(wh_task *t, int no_repeat_ngram_size, float repetition_penalty, void *stream);
 /* number of cached self-attention positions of the longest row (the `offset` of model.py:234) */
 int wh_task_position(const wh_task *t);
 /* Introspection for tests and the benchmark.  what = 0: 1 when this task's decode step runs the cross attention with its

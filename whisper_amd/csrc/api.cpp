@@ -306,6 +306,7 @@ struct wh_task {
   wh_phrases phrases; bool phrases_on;
   int* phrase_root;        // [V] root child reached by every token, -1 = none
   int* phrase_span;        // [R][2] child_begin pair of every row's node ({0, 0} at the root)
+  RepArgs rep; bool rep_on;       // repetition control (wh_task_set_repetition) of the loops begun from now on
   void* beam_scratch;      // beam search partials / candidates (G > 1)
   int* beam_flags;         // [2][B] completion flags + [1] applied-update counter
   int* beam_lcp;           // [B][8][8] shared-history lengths of the rows of a segment + [R] first position to copy
@@ -336,6 +337,7 @@ struct wh_loop {
   // loop state
   SampleArgs sa; BeamArgs ba;
   PhraseArgs ph; bool biased;        // the greedy sampler's phrase arguments, when the task had a list at the loop's start
+  RepArgs rep; bool rep_on;          // likewise its repetition control
   bool fused_embed, pending, wait_due;
   int ntok, steps, ntok_at_copy, cur;
   int n_tokens;                      // result
@@ -554,6 +556,7 @@ static int task_reset_impl(wh_task* t, void* stream_) {
     t->lag_on = false;
   }
   t->phrases_on = false;                         // the sampler reads the derived tables only while a list is set
+  t->rep_on = false; t->rep = RepArgs{0, 1.0f};
   t->needs_reset = false;
   return WH_OK;
 }
@@ -596,6 +599,19 @@ extern "C" int wh_task_set_phrases(wh_task* t, const wh_phrases* p, void* stream
                                   t->phrase_root, (hipStream_t)stream));
   t->phrases = *p;
   t->phrases_on = true;
+  return WH_OK;
+}
+
+// Repetition control for the device-side greedy / sampling loop (sampling.hip, REP).  Nothing lives on the device: the
+// two numbers travel as kernel arguments of the loops begun after the call, which is all "stream-ordered" has to mean.
+extern "C" int wh_task_set_repetition(wh_task* t, int no_repeat_ngram_size, float repetition_penalty, void* stream) {
+  TASK_ENTER(t);
+  if (!t) return WH_ERR_ARG;
+  if (no_repeat_ngram_size < 0 || no_repeat_ngram_size > WH_REPETITION_MAX_NGRAM) return WH_ERR_ARG;
+  if (!std::isfinite(repetition_penalty) || !(repetition_penalty > 0.f)) return WH_ERR_ARG;
+  if (t->needs_reset) { const int rc = task_reset_impl(t, stream); if (rc != WH_OK) return rc; }
+  t->rep = RepArgs{no_repeat_ngram_size, repetition_penalty};
+  t->rep_on = no_repeat_ngram_size != 0 || repetition_penalty != 1.0f;
   return WH_OK;
 }
 
@@ -1231,6 +1247,7 @@ static int greedy_start(wh_task* t) {
     ph.n_nodes = t->phrases.n_nodes; ph.n_edges = t->phrases.n_edges; ph.boost = t->phrases.boost;
     HIPCHK(hipMemsetAsync(t->phrase_span, 0, (size_t)R * 8, s));
   }
+  L->rep_on = t->rep_on; L->rep = t->rep;      // stateless: a hand-off fallback's re-run needs nothing put back
   // the sampler also writes the next step's input row (token embedding + position): the step graph starts at layer 0
   L->fused_embed = !WH_DEV_FLAG("WH_NO_FUSED_EMBED");   // developer A/B switch
   if (L->fused_embed) {
@@ -1242,7 +1259,7 @@ static int greedy_start(wh_task* t) {
     sa.seed_lo = (uint32_t)(p->seed & 0xffffffffu); sa.seed_hi = (uint32_t)(p->seed >> 32);
   }
   sa.logits = t->logits + (size_t)(n_sel - 1) * V; sa.logits_ld = (int64_t)n_sel * V;
-  HIPCHK(launch_greedy_sample(sa, s, L->biased ? &ph : nullptr));
+  HIPCHK(launch_greedy_sample(sa, s, L->biased ? &ph : nullptr, L->rep_on ? &L->rep : nullptr));
   sa.logits = t->logits; sa.logits_ld = V;
   L->ntok = T0 + 1; L->steps = 1;
   L->pending = L->wait_due = false; L->ntok_at_copy = 0;
@@ -1375,7 +1392,7 @@ static int loop_pump(wh_task* t, bool block) {
         if (!(L->steps < p->max_steps && L->ntok <= p->n_ctx && L->ntok <= d.n_text_ctx)) break;
         int rc = step_run(t, s, t->loop_kind == LOOP_GREEDY && L->fused_embed);
         if (rc != WH_OK) return rc;
-        if (t->loop_kind == LOOP_GREEDY) HIPCHK(launch_greedy_sample(L->sa, s, L->biased ? &L->ph : nullptr));
+        if (t->loop_kind == LOOP_GREEDY) HIPCHK(launch_greedy_sample(L->sa, s, L->biased ? &L->ph : nullptr, L->rep_on ? &L->rep : nullptr));
         else { rc = beam_update(t, t->logits, d.n_vocab, 0); if (rc != WH_OK) return rc; }
         ++L->ntok; ++L->steps;
         if (L->pending && (L->steps & 7) == 2) L->wait_due = true;
@@ -1440,6 +1457,7 @@ static int beam_check(const wh_task* t, const wh_beam_params* bp, const int64_t*
                       const int32_t* fin_count) {
   if (!t || !bp || !tokens || !sum_logprobs || !fin_tokens || !fin_len || !fin_scores || !fin_count) return WH_ERR_ARG;
   if (t->phrases_on) return WH_ERR_STATE;      // the beam loop does not carry trie nodes through its row permutation
+  if (t->rep_on) return WH_ERR_STATE;          // nor does beam.hip apply repetition control (the host loop's filters do)
   const wh_greedy_params* p = &bp->rules;
   const wh_dims& d = t->m->d;
   const int R = t->R, G = t->G, T0 = p->sample_begin;

@@ -297,9 +297,22 @@ struct PhraseArgs {
   int n_nodes, n_edges;
   float boost;
 };
+// Repetition control inside the sampler (include/whisper_hip.h, wh_task_set_repetition).  It carries no state: both edits
+// follow from the row's sampled tokens H = tokens[r][sample_begin - lag[r] .. length), which the partial kernel reads.
+//   penalty != 1: every token of H below eot, as a SET, has its raw logit divided by `penalty` if positive, multiplied if
+//                 negative (0 and -inf stay);
+//   ngram >= 1:   every token below eot that followed an earlier occurrence of the row's last ngram - 1 tokens is -inf.
+// Order: penalty -> phrase boost -> ban -> SuppressBlank / SuppressTokens / ApplyTimestampRules.
+constexpr int REP_MAX_NGRAM = 16;
+struct RepArgs {
+  int ngram;                  // 0: off
+  float penalty;              // 1: off; finite and > 0
+};
 size_t greedy_sample_scratch_bytes(int R, int V);
-// ph == nullptr: the unbiased instantiations, which never look at the phrase arguments
-hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const PhraseArgs* ph = nullptr);
+// ph == nullptr: the unbiased instantiations, which never look at the phrase arguments; rep == nullptr (or {0, 1}): the
+// instantiations without repetition control, which never look at the row's history for it
+hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const PhraseArgs* ph = nullptr,
+                                const RepArgs* rep = nullptr);
 // root[v] = child of the root reached by token v, else -1 (tokens outside [0, V) are ignored)
 hipError_t launch_phrase_root_table(const int* child_begin, const int* child_token, const int* child_node, int n_edges,
                                     int V, int* root, hipStream_t stream);

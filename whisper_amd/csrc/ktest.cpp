@@ -136,6 +136,36 @@ int wht_greedy_sample(const float* logits, int64_t logits_ld, int R, int V, int6
   if (e != hipSuccess) return e;
   return launch_greedy_sample(a, (hipStream_t)stream, &ph);
 }
+// the same two launches with repetition control (RepArgs) and, where child_begin is given, a phrase list as well
+int wht_greedy_sample_rep(const float* logits, int64_t logits_ld, int R, int V, int64_t* tokens, int64_t token_stride,
+                          const int* d_ntok, const int* lag, int sample_begin, int eot, int timestamp_begin, int no_timestamps,
+                          int max_initial_ts, int suppress_blank, int blank_token, const uint8_t* suppress_mask,
+                          float* sum_logprobs, int64_t* step_tokens, int* d_alive_step, float* partials, size_t partials_bytes,
+                          float temperature, uint64_t seed, int* row_state, int n_nodes, int n_edges, const int* child_begin,
+                          const int* child_token, const int* child_node, const int* root_child, int* span, float boost,
+                          int no_repeat_ngram_size, float repetition_penalty, void* stream) {
+  if (R < 1 || V < 1 || partials_bytes < greedy_sample_scratch_bytes(R, V)) return hipErrorInvalidValue;
+  SampleArgs a;
+  memset(&a, 0, sizeof a);
+  a.logits = logits; a.logits_ld = logits_ld; a.R = R; a.V = V; a.tokens = tokens; a.token_stride = token_stride;
+  a.d_ntok = d_ntok; a.lag = lag; a.sample_begin = sample_begin; a.eot = eot; a.timestamp_begin = timestamp_begin;
+  a.no_timestamps = no_timestamps; a.max_initial_ts = max_initial_ts; a.suppress_blank = suppress_blank;
+  a.blank_token = blank_token; a.suppress_mask = suppress_mask; a.sum_logprobs = sum_logprobs; a.step_tokens = step_tokens;
+  a.d_alive_step = d_alive_step; a.partials = partials; a.row_state = row_state;
+  if (temperature > 0.f) {
+    a.inv_temperature = 1.0f / temperature;
+    a.seed_lo = (uint32_t)(seed & 0xffffffffu); a.seed_hi = (uint32_t)(seed >> 32);
+  }
+  const RepArgs rep{no_repeat_ngram_size, repetition_penalty};
+  if (!child_begin) return launch_greedy_sample(a, (hipStream_t)stream, nullptr, &rep);
+  PhraseArgs ph;
+  memset(&ph, 0, sizeof ph);
+  ph.child_begin = child_begin; ph.child_token = child_token; ph.child_node = child_node; ph.root_child = root_child;
+  ph.span = span; ph.n_nodes = n_nodes; ph.n_edges = n_edges; ph.boost = boost;
+  const hipError_t e = launch_phrase_span(row_state, child_begin, n_nodes, R, span, (hipStream_t)stream);
+  if (e != hipSuccess) return e;
+  return launch_greedy_sample(a, (hipStream_t)stream, &ph, &rep);
+}
 size_t wht_greedy_sample_scratch_bytes(int R, int V) { return greedy_sample_scratch_bytes(R, V); }
 int wht_phrase_root_table(const int* child_begin, const int* child_token, const int* child_node, int n_edges, int V, int* root,
                           void* stream) {

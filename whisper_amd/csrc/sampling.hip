@@ -88,11 +88,24 @@ constexpr int PSTRIDE = 8;      // floats per (row, chunk, range) partial: m, s,
 // `span` (left by the previous step's final kernel) and is asked for in the same batch.  Only the node's child tokens come
 // one round trip later: 64 per wave in one coalesced load, of which those inside this workgroup's 1024-entry slice (usually
 // none: the children of a node fall into few of the ~50 slices) are handed round as wave-uniform values.
-template <bool SAMPLE, bool BIAS>
-__global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, int nchunk, whk::PhraseArgs ph) {
+// REP (repetition control, kernels.h RepArgs): stateless — everything comes from the row's own sampled tokens H, which the
+// workgroup walks in tiles of 256 (one token per thread, one dependent round trip behind the position counter).  A token
+// of H below eot that falls into this workgroup's slice sets its bit in `sh_pen` (the penalised SET: a token seen five times
+// is marked once); where the ngram - 1 tokens before it equal the row's last ngram - 1 tokens it also sets its bit in
+// `sh_ban`.  The contexts are compared in LDS (`sh_hist` keeps a tile and the 16 tokens before it), and only for the few
+// tokens of the slice.  Penalty on the raw logit -> boost -> ban, all ahead of the stock filters.
+constexpr int HTILE = 256;      // tokens of a row's history per pass (== the workgroup size)
+constexpr int HLEAD = 16;       // tokens kept in front of a tile: the longest context (REP_MAX_NGRAM - 1) rounded up
+static_assert(whk::REP_MAX_NGRAM - 1 <= HLEAD, "a context must fit in front of a tile");
+template <bool SAMPLE, bool BIAS, bool REP>
+__global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, int nchunk, whk::PhraseArgs ph, whk::RepArgs rp) {
   pin_kernargs(a);
   if constexpr (BIAS) pin_kernargs(ph);
+  if constexpr (REP) pin_kernargs(rp);
   asm volatile("" ::"s"(nchunk));
+  __shared__ int sh_hist[REP ? HLEAD + HTILE : 1];
+  __shared__ int sh_suffix[REP ? HLEAD : 1];
+  __shared__ unsigned sh_pen[REP ? SCHUNK / 32 : 1], sh_ban[REP ? SCHUNK / 32 : 1];
   __shared__ int sh_last_ts;
   __shared__ float sh_m[2][4], sh_s[2][4];
   __shared__ int sh_i[2][4];
@@ -172,6 +185,37 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
     }
   }
 
+  if constexpr (REP) {
+    const int nctx = rp.ngram > 0 ? rp.ngram - 1 : 0;      // context length; ngram == 0: no ban
+    const bool ban_on = rp.ngram > 0 && L >= nctx, pen_on = rp.penalty != 1.0f;
+    const int lo = c * SCHUNK;
+    if (tid < SCHUNK / 32) { sh_pen[tid] = 0u; sh_ban[tid] = 0u; }
+    if (ban_on && tid < nctx) sh_suffix[tid] = (int)row[ntok - nctx + tid];        // s = the last ngram - 1 tokens of H
+    // Every workgroup of the row walks the WHOLE history, also one whose slice turns out to hold none of the row's tokens:
+    // which slices they fall in is only known after reading them.  The cost of the feature therefore grows with L in all
+    // of a row's workgroups (V / 1024 of them), not only in those that end up with a bit set.
+    for (int base = 0; base < L; base += HTILE) {          // L is workgroup-uniform
+      const int g = base + tid;                            // this thread's position in H
+      const int tok = g < L ? (int)row[sample_begin + g] : -1;
+      int lead = -1;
+      if (tid < HLEAD && base + tid - HLEAD >= 0) lead = (int)row[sample_begin + base + tid - HLEAD];
+      if (base > 0) __syncthreads();                       // the previous tile has been compared
+      sh_hist[HLEAD + tid] = tok;
+      if (tid < HLEAD) sh_hist[tid] = lead;
+      __syncthreads();
+      const unsigned d = (unsigned)(tok - lo);
+      if (g < L && tok >= 0 && tok < a.eot && d < (unsigned)SCHUNK) {
+        if (pen_on) atomicOr(&sh_pen[d >> 5], 1u << (d & 31));
+        if (ban_on && g >= nctx) {                         // H[g - nctx .. g - 1] == s ?  (i = g - nctx <= L - ngram)
+          bool same = true;
+          for (int q = 0; q < nctx; ++q) same = same && sh_hist[HLEAD + tid - nctx + q] == sh_suffix[q];
+          if (same) atomicOr(&sh_ban[d >> 5], 1u << (d & 31));
+        }
+      }
+    }
+    __syncthreads();
+  }
+
   Stat st[2];
   st[0] = Stat{WH_NEG_INF, 0.f, 0x7fffffff};
   st[1] = Stat{WH_NEG_INF, 0.f, 0x7fffffff};
@@ -197,8 +241,17 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
         if (a.max_initial_ts >= 0 && v > TB + a.max_initial_ts) masked = true;
       }
     }
+    if constexpr (REP) {
+      if ((sh_ban[(j * 256 + tid) >> 5] >> (tid & 31)) & 1u) masked = true;      // NoRepeatNGram: -inf, like a suppressed token
+    }
     if (masked) continue;
     float xj = xv[j];
+    if constexpr (REP) {                       // RepetitionPenalty: on the raw logit, ahead of the boost
+      if ((sh_pen[(j * 256 + tid) >> 5] >> (tid & 31)) & 1u) {
+        if (xj > 0.f) xj = xj / rp.penalty;
+        else if (xj < 0.f) xj = xj * rp.penalty;
+      }
+    }
     if constexpr (BIAS) { if (hit[j]) xj += ph.boost; }
     if (v < split) stat_add(st[0], xj, v); else stat_add(st[1], xj, v);
     if constexpr (SAMPLE) {
@@ -461,26 +514,34 @@ namespace whk {
 size_t greedy_sample_scratch_bytes(int R, int V) { return (size_t)R * ((V + SCHUNK - 1) / SCHUNK) * 2 * PSTRIDE * sizeof(float); }
 
 template <bool SAMPLE, bool BIAS>
-static void greedy_sample_launch(const SampleArgs& a, const PhraseArgs& ph, int nchunk, hipStream_t stream) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS>), dim3(nchunk, a.R), dim3(256), 0, stream, a, nchunk, ph);
+static void greedy_sample_launch(const SampleArgs& a, const PhraseArgs& ph, const RepArgs* rep, int nchunk, hipStream_t stream) {
+  if (rep)      // repetition control lives in the partial kernel alone: the final kernel is the same with and without it
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS, true>), dim3(nchunk, a.R), dim3(256), 0, stream, a, nchunk, ph, *rep);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS, false>), dim3(nchunk, a.R), dim3(256), 0, stream, a, nchunk, ph, RepArgs{0, 1.0f});
   hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_final_kernel<SAMPLE, BIAS>), dim3(a.R), dim3(256), 0, stream, a, nchunk, ph);
 }
 
-hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const PhraseArgs* ph) {
+hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const PhraseArgs* ph, const RepArgs* rep) {
   const int nchunk = (a.V + SCHUNK - 1) / SCHUNK;
   if (!a.partials) return hipErrorInvalidValue;
   const bool sample = a.inv_temperature > 0.f;
+  if (rep) {
+    if (rep->ngram < 0 || rep->ngram > REP_MAX_NGRAM || !(rep->penalty > 0.f) || !(rep->penalty <= 3.402823466e38f))
+      return hipErrorInvalidValue;
+    if (rep->ngram == 0 && rep->penalty == 1.0f) rep = nullptr;      // both off: the kernels of a plain decode
+  }
   if (ph) {
     if (!ph->child_begin || !ph->child_token || !ph->child_node || !ph->root_child || !ph->span || !a.row_state ||
         ph->n_nodes < 1 || ph->n_edges < 0)
       return hipErrorInvalidValue;
-    if (sample) greedy_sample_launch<true, true>(a, *ph, nchunk, stream);
-    else greedy_sample_launch<false, true>(a, *ph, nchunk, stream);
+    if (sample) greedy_sample_launch<true, true>(a, *ph, rep, nchunk, stream);
+    else greedy_sample_launch<false, true>(a, *ph, rep, nchunk, stream);
   } else {
     PhraseArgs none;
     memset(&none, 0, sizeof(none));
-    if (sample) greedy_sample_launch<true, false>(a, none, nchunk, stream);
-    else greedy_sample_launch<false, false>(a, none, nchunk, stream);
+    if (sample) greedy_sample_launch<true, false>(a, none, rep, nchunk, stream);
+    else greedy_sample_launch<false, false>(a, none, rep, nchunk, stream);
   }
   return hipGetLastError();
 }

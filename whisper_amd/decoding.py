@@ -488,6 +488,92 @@ class PhraseBias(LogitFilter):
             logits[torch.tensor(idx_r, device=logits.device), torch.tensor(idx_c, device=logits.device)] += ph.boost
 
 
+MAX_NO_REPEAT_NGRAM = 16        # WH_REPETITION_MAX_NGRAM (include/whisper_hip.h)
+
+
+def check_repetition(no_repeat_ngram_size=0, repetition_penalty=1.0) -> Tuple[int, float]:
+    """the two repetition-control options as (int, float); ValueError for a size outside 0 .. 16 or not an integer, or a
+    penalty that is not finite or is <= 0"""
+    n, p = no_repeat_ngram_size, repetition_penalty
+    if n is None:
+        n = 0
+    if p is None:
+        p = 1.0
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= MAX_NO_REPEAT_NGRAM:
+        raise ValueError(f"no_repeat_ngram_size must be an integer from 0 (off) to {MAX_NO_REPEAT_NGRAM} (got {n!r})")
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not np.isfinite(p) or p <= 0:
+        raise ValueError(f"repetition_penalty must be a finite number above 0, 1.0 = off (got {p!r})")
+    return int(n), float(p)
+
+
+def _row_histories(tokens: Tensor, sample_begin: int, row_begin: Optional[Sequence[int]]) -> List[List[int]]:
+    """every row's sampled tokens: `tokens[r, sample_begin:]`, or from `row_begin[r]` where the prompts differ in length"""
+    rows = tokens.tolist()
+    if row_begin is not None and len(row_begin) != len(rows):
+        raise ValueError(f"{len(row_begin)} sample_begin values for {len(rows)} rows")
+    return [row[(row_begin[r] if row_begin is not None else sample_begin):] for r, row in enumerate(rows)]
+
+
+class RepetitionPenalty(LogitFilter):
+    """`repetition_penalty` of other Whisper runtimes.  For every row, each token below <|endoftext|> among the row's SAMPLED
+    tokens (`tokens[row, sample_begin:]`, timestamps included, prompt and prefix not) — as a set: a token seen five times is
+    penalised once — has its raw logit divided by `penalty` if positive and multiplied by it if negative; 0 and -inf stay.
+    It goes FIRST in `logit_filters`, ahead of PhraseBias: the penalty acts on the raw logit.  This is the host-loop form; the
+    device-side greedy / sampling loop applies the same rule inside its sampler (csrc/sampling.hip).
+    `row_begin`: per-row `sample_begin` for rows whose prompts differ in length."""
+
+    def __init__(self, penalty: float, eot: int, sample_begin: int, row_begin: Optional[Sequence[int]] = None):
+        _, self.penalty = check_repetition(0, penalty)
+        self.eot = eot
+        self.sample_begin = sample_begin
+        self.row_begin = list(row_begin) if row_begin is not None else None
+
+    def apply(self, logits: Tensor, tokens: Tensor):
+        idx_r, idx_c = [], []
+        for r, hist in enumerate(_row_histories(tokens, self.sample_begin, self.row_begin)):
+            seen = sorted({t for t in hist if 0 <= t < self.eot})
+            idx_r.extend([r] * len(seen))
+            idx_c.extend(seen)
+        if not idx_r:
+            return
+        ir, ic = torch.tensor(idx_r, device=logits.device), torch.tensor(idx_c, device=logits.device)
+        x = logits[ir, ic]
+        logits[ir, ic] = torch.where(x > 0, x / self.penalty, torch.where(x < 0, x * self.penalty, x))
+
+
+class NoRepeatNGram(LogitFilter):
+    """`no_repeat_ngram_size` of other Whisper runtimes.  With H a row's sampled tokens (as for RepetitionPenalty), L = |H|
+    and s the last n - 1 of them (empty for n = 1): if L >= n - 1, every token H[i + n - 1] below <|endoftext|> with
+    0 <= i <= L - n and H[i .. i + n - 2] == s becomes -inf.  Timestamps and specials take part in the contexts but ids
+    >= eot are never banned, so <|endoftext|> stays available.  It goes behind PhraseBias and ahead of SuppressBlank.
+    Stateless, so beam search's row permutation needs no hook.  `row_begin`: as in RepetitionPenalty."""
+
+    def __init__(self, ngram_size: int, eot: int, sample_begin: int, row_begin: Optional[Sequence[int]] = None):
+        self.n, _ = check_repetition(ngram_size, 1.0)
+        if self.n < 1:
+            raise ValueError("NoRepeatNGram needs an n-gram size of at least 1")
+        self.eot = eot
+        self.sample_begin = sample_begin
+        self.row_begin = list(row_begin) if row_begin is not None else None
+
+    def banned(self, hist: Sequence[int]) -> List[int]:
+        n, L = self.n, len(hist)
+        if L < n - 1:
+            return []
+        s = list(hist[L - (n - 1):])
+        return sorted({hist[i + n - 1] for i in range(L - n + 1)
+                       if list(hist[i: i + n - 1]) == s and 0 <= hist[i + n - 1] < self.eot})
+
+    def apply(self, logits: Tensor, tokens: Tensor):
+        idx_r, idx_c = [], []
+        for r, hist in enumerate(_row_histories(tokens, self.sample_begin, self.row_begin)):
+            ban = self.banned(hist)
+            idx_r.extend([r] * len(ban))
+            idx_c.extend(ban)
+        if idx_r:
+            logits[torch.tensor(idx_r, device=logits.device), torch.tensor(idx_c, device=logits.device)] = -np.inf
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # the task
 # ---------------------------------------------------------------------------------------------------------------
@@ -501,8 +587,14 @@ class DecodingTask:
     logit_filters: List[LogitFilter]
 
     def __init__(self, model: "Whisper", options: DecodingOptions, prompts: Optional[Sequence[Sequence[int]]] = None,
-                 phrases: Optional[Union[PhraseList, Sequence]] = None):
-        """`phrases` (no counterpart in the reference; it travels as a keyword because DecodingOptions keeps the reference's
+                 phrases: Optional[Union[PhraseList, Sequence]] = None, no_repeat_ngram_size: int = 0,
+                 repetition_penalty: float = 1.0):
+        """`no_repeat_ngram_size` / `repetition_penalty` (no counterpart in the reference; keywords, because DecodingOptions
+        keeps the reference's fields): repetition control over a row's SAMPLED tokens — timestamps included, prompt and
+        prefix not, so text of the previous window stays repeatable; ids >= <|endoftext|> are never banned or penalised
+        (NoRepeatNGram, RepetitionPenalty).  0 / 1.0 are off.  Greedy decoding and sampling apply both inside the
+        device-side loop; beam search runs the host loop with the two filters.
+        `phrases` (no counterpart in the reference; it travels as a keyword because DecodingOptions keeps the reference's
         fields): a `PhraseList`, or a plain list of strings / token-id lists compiled at the default boost — phrases the
         decoder should prefer (phrases.py).  Greedy decoding and sampling apply it inside the device-side loop; beam search
         runs the host loop with the `PhraseBias` filter.
@@ -567,6 +659,17 @@ class DecodingTask:
             if self.row_lag is not None and any(self.row_lag):
                 row_begin = [self.sample_begin - lag for lag in self.row_lag for _ in range(self.n_group)]
             self.logit_filters.insert(0, PhraseBias(self.phrases, self.sample_begin, row_begin))
+        # RepetitionPenalty -> PhraseBias -> NoRepeatNGram -> SuppressBlank -> SuppressTokens -> ApplyTimestampRules
+        self.no_repeat_ngram_size, self.repetition_penalty = check_repetition(no_repeat_ngram_size, repetition_penalty)
+        if self.no_repeat_ngram_size or self.repetition_penalty != 1.0:
+            row_begin = None
+            if self.row_lag is not None and any(self.row_lag):
+                row_begin = [self.sample_begin - lag for lag in self.row_lag for _ in range(self.n_group)]
+            if self.no_repeat_ngram_size:
+                self.logit_filters.insert(1 if self.phrases is not None else 0,
+                                          NoRepeatNGram(self.no_repeat_ngram_size, tokenizer.eot, self.sample_begin, row_begin))
+            if self.repetition_penalty != 1.0:
+                self.logit_filters.insert(0, RepetitionPenalty(self.repetition_penalty, tokenizer.eot, self.sample_begin, row_begin))
         self._stock_filters = list(self.logit_filters)
 
     def _verify_options(self, options: DecodingOptions) -> DecodingOptions:
@@ -647,7 +750,8 @@ class DecodingTask:
         return (type(self.decoder) is GreedyDecoder and self.options.temperature >= 0
                 and (self.n_group == 1 or self.options.temperature > 0)
                 and type(self.inference) is HipInference and self.logit_filters == self._stock_filters
-                and all(type(f) in (PhraseBias, SuppressBlank, SuppressTokens, ApplyTimestampRules) for f in self.logit_filters)
+                and all(type(f) in (RepetitionPenalty, PhraseBias, NoRepeatNGram, SuppressBlank, SuppressTokens, ApplyTimestampRules)
+                        for f in self.logit_filters)
                 and self.sample_begin + self.sample_len <= 2 * self.n_ctx)
 
     def _beam_shape_ok(self) -> bool:
@@ -755,6 +859,8 @@ class DecodingTask:
                 task.set_lag(row_lag)
             if self.phrases is not None:         # PhraseBias, inside the sampler (the task forgets the list when it is reset)
                 task.set_phrases(self.phrases.device_arrays(dev), self.phrases.boost)
+            if self.no_repeat_ngram_size or self.repetition_penalty != 1.0:     # likewise forgotten at reset
+                task.set_repetition(self.no_repeat_ngram_size, self.repetition_penalty)
             if wait:
                 res = task.greedy(buf, params, self.sot_index, no_speech)
             else:
@@ -937,12 +1043,13 @@ def decode(model: "Whisper", mel: Tensor, options: DecodingOptions = DecodingOpt
     parameter list stays the reference's plus `prompts`): a phrase list to prefer, a `PhraseList` or a plain list of strings
     (see DecodingTask); the other keywords replace fields of `options`."""
     phrases = kwargs.pop("phrases", None)
+    repetition = {k: kwargs.pop(k) for k in ("no_repeat_ngram_size", "repetition_penalty") if k in kwargs}
     single = mel.ndim == 2
     if single:
         mel = mel.unsqueeze(0)
     if kwargs:
         options = replace(options, **kwargs)
-    result = DecodingTask(model, options, prompts, phrases).run(mel)
+    result = DecodingTask(model, options, prompts, phrases, **repetition).run(mel)
     return result[0] if single else result
 
 
@@ -1224,7 +1331,7 @@ def coalesce_batches(rows: Sequence[int], chain_rows: Optional[int]) -> List[Lis
 
 def decode_many(model: "Whisper", mels: Sequence[Tensor], options: DecodingOptions = DecodingOptions(), in_flight: int = 3,
                 chain_rows: Optional[int] = 24, phrases: Optional[Union[PhraseList, Sequence]] = None,
-                **kwargs) -> List[List[DecodingResult]]:
+                no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, **kwargs) -> List[List[DecodingResult]]:
     """`decode(model, mel, options)` for every batch of `mels` — each a (B, n_mels, 3000) tensor, or raw (B, 480000) audio (its
     log-mel is then taken here, per batch: audio.py:155 clamps against the maximum over the tensor it is given) — scheduled for
     throughput; returns the per-batch result lists in order.  No counterpart in the reference.  Two levers:
@@ -1238,7 +1345,8 @@ def decode_many(model: "Whisper", mels: Sequence[Tensor], options: DecodingOptio
       * `in_flight`: up to this many chains are decoded at once, each on a HIP stream of its own, all driven from the calling
         thread (`run_interleaved`): chains of few rows leave the chip idle between their dependent launches and fill each other's
         gaps.  Chains of 16+ rows of a large model gain little from it.
-    `phrases`: one phrase list for all batches (see DecodingTask)."""
+    `phrases`: one phrase list for all batches (see DecodingTask); `no_repeat_ngram_size` / `repetition_penalty` likewise."""
+    repetition = dict(zip(("no_repeat_ngram_size", "repetition_penalty"), check_repetition(no_repeat_ngram_size, repetition_penalty)))
     if kwargs:
         options = replace(options, **kwargs)
     if phrases is not None and not isinstance(phrases, PhraseList):      # compiled once, shared by every chain
@@ -1263,7 +1371,7 @@ def decode_many(model: "Whisper", mels: Sequence[Tensor], options: DecodingOptio
                 from .audio import log_mel_spectrogram
                 x = log_mel_spectrogram(x, model.dims.n_mels)
             parts.append(x.to(dtype))
-        res = yield from DecodingTask(model, options, phrases=phrases).run_steps(parts[0] if len(parts) == 1 else torch.cat(parts), wait=False)
+        res = yield from DecodingTask(model, options, phrases=phrases, **repetition).run_steps(parts[0] if len(parts) == 1 else torch.cat(parts), wait=False)
         out, at = [], 0
         for p_ in parts:
             out.append(res[at: at + p_.shape[0]])

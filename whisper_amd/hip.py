@@ -122,6 +122,7 @@ SIGNATURES = {
     "wh_task_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "wh_task_set_lag": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "wh_task_set_phrases": (C.c_int, [C.c_void_p, C.POINTER(Phrases), C.c_void_p]),
+    "wh_task_set_repetition": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "wh_task_position": (C.c_int, [C.c_void_p]),
     "wh_task_info": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "wh_task_greedy": (C.c_int, [C.c_void_p, C.POINTER(GreedyParams), C.c_void_p, C.c_int64, C.c_int, C.c_int,
@@ -784,6 +785,14 @@ class HipTask:
         for a in (begin, token, node):
             a.record_stream(self.stream)
         self._phrase_arrays = (begin, token, node)
+
+    def set_repetition(self, no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0):
+        """repetition control of the device-side greedy / sampling loop (wh_task_set_repetition): no token that would
+        complete an n-gram the row has already sampled, and / or a penalty on the logits of the tokens the row has sampled;
+        (0, 1.0) clears, and so does `reset`"""
+        with self._call():
+            check(lib().wh_task_set_repetition(self.handle, int(no_repeat_ngram_size), float(repetition_penalty),
+                                               stream_ptr(self.stream)), "wh_task_set_repetition")
 
     def set_lag(self, lag: Optional[Sequence[int]]):
         """ragged prompts: row r's sequence is the longest row's shifted left by lag[r] (include/whisper_hip.h)"""

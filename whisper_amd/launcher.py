@@ -106,7 +106,10 @@ def transcribe_sharded(model, audios: Sequence[Any], dist=None, *, batch_size: i
     one file never leave their rank: seek and prompt depend on the previous window, transcribe.py:288-293,371-399);
     rank 0 returns the result dicts in input order, other ranks None.  All inputs must be of one kind (arrays or
     paths) for the costs to be comparable.  `device_ingest`: every rank loads its files on its own GPU (transcribe_batch).
-    `phrases` / `phrase_boost` among the keywords: one phrase list for all files, compiled on every rank (transcribe_batch)."""
+    `phrases` / `phrase_boost` among the keywords: one phrase list for all files, compiled on every rank (transcribe_batch);
+    `no_repeat_ngram_size` / `repetition_penalty` among them as well: repetition control on every rank (transcribe)."""
+    from .decoding import check_repetition
+    check_repetition(kwargs.get("no_repeat_ngram_size", 0), kwargs.get("repetition_penalty", 1.0))     # before any rank starts work
     from .transcribe import transcribe_batch
     costs = [_audio_cost(a) for a in audios]
     if device_ingest:

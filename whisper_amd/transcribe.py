@@ -84,6 +84,21 @@ def _phrases_kw(phrases) -> dict:
     return {} if phrases is None else {"phrases": phrases}
 
 
+def _pop_repetition(options: dict) -> dict:
+    """take `no_repeat_ngram_size` / `repetition_penalty` out of a keyword dict (no DecodingOptions fields either) and check
+    them (ValueError); returns the keywords for `model.decode` — none while both are off, so that the call is then the one
+    made before the options existed"""
+    from .decoding import check_repetition
+    n, p = check_repetition(options.pop("no_repeat_ngram_size", 0), options.pop("repetition_penalty", 1.0))
+    return {} if (n == 0 and p == 1.0) else {"no_repeat_ngram_size": n, "repetition_penalty": p}
+
+
+def _check_repetition(kwargs: dict) -> None:
+    """argument errors of the two options before any work of a batched call (they stay among the keywords)"""
+    from .decoding import check_repetition
+    check_repetition(kwargs.get("no_repeat_ngram_size", 0), kwargs.get("repetition_penalty", 1.0))
+
+
 def _compile_phrases(model: "Whisper", kwargs: dict) -> None:
     """replace a plain `phrases` list among the keywords by its PhraseList, once for all the files / chunks of a call"""
     compiled = _pop_phrases(model, kwargs)
@@ -111,6 +126,7 @@ class _Transcriber:
         # a phrase list is no DecodingOptions field (those stay the reference's): it leaves the keywords here and goes to
         # every decode of this file — every window, every rung of the temperature ladder — as `phrases=`
         self.phrases = _pop_phrases(model, decode_options)
+        self.repetition = _pop_repetition(decode_options)      # likewise: every window, every rung
         self.decode_options = decode_options
         self.initial_prompt = initial_prompt
         self.clip_timestamps = clip_timestamps
@@ -121,7 +137,7 @@ class _Transcriber:
         (reference transcribe.py:184-224); `first` skips temperatures already tried by a batched pass"""
         result = None
         for t in self.temperatures[first:]:
-            result = self.model.decode(segment, self._options_for(t), **_phrases_kw(self.phrases))
+            result = self.model.decode(segment, self._options_for(t), **_phrases_kw(self.phrases), **self.repetition)
             if not self._needs_retry(result):
                 break
             feats = getattr(result, "audio_features", None)
@@ -424,6 +440,10 @@ def transcribe(
     `phrases` / `phrase_boost` (likewise among the keywords): phrases the decoder should prefer — a `phrases.PhraseList`, or a
     list of strings compiled with `phrase_boost` (default 3.0 logit units); applied to every window and every rung of the
     temperature ladder (phrases.py; inside the device-side loop for greedy decoding and sampling).
+    `no_repeat_ngram_size` / `repetition_penalty` (likewise among the keywords; 0 / 1.0 = off): repetition control over the
+    tokens SAMPLED in a window — never over the prompt, so a sentence said in two windows stays possible — applied to every
+    window and every rung of the temperature ladder (decoding.NoRepeatNGram / RepetitionPenalty; inside the device-side
+    loop for greedy decoding and sampling).
     """
     if decode_options.pop("device_ingest", False) and isinstance(audio, str):
         audio = load_audio(audio, device=model.device)
@@ -456,12 +476,12 @@ def _options_key(opts: dict):
 
 
 def _prompt_batches(model: "Whisper", options: DecodingOptions, prompts: List[Optional[List[int]]], members: List[int],
-                    batch_size: int, phrases=None) -> List[List[int]]:
+                    batch_size: int, phrases=None, repetition: Optional[dict] = None) -> List[List[int]]:
     """split `members` (windows with the same options and the prompts `prompts[i]`) into batches one DecodingTask
     can take: rows whose initial sequences have different lengths may share a call in the device-side modes (greedy,
     sampling, beam search with the stock decoder / filters) below the length limit (DecodingTask.ragged_limit: no row
     may reach the context limit before the step budget ends); any rows of EQUAL length may always share one"""
-    probe = DecodingTask(model, options, phrases=phrases)       # (beam search with a phrase list runs the host loop: no ragged rows)
+    probe = DecodingTask(model, options, phrases=phrases, **(repetition or {}))       # (beam search with a phrase list runs the host loop: no ragged rows)
     limit = probe.ragged_limit()
     classes = {}
     for i in members:
@@ -527,9 +547,11 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
     the decoder's weights once for all its rows.  Worth it from about 2 * batch_size files on.
     `device_ingest`: file paths are loaded as `load_audio(path, device=model.device)` loads them (WAV / FLAC down-mixed,
     resampled and quantised on the GPU); the host-side parsing / FLAC decoding stays on the loader threads.
-    `phrases` / `phrase_boost`: as in `transcribe`; one phrase list for all files."""
+    `phrases` / `phrase_boost`: as in `transcribe`; one phrase list for all files.  `no_repeat_ngram_size` /
+    `repetition_penalty`: as in `transcribe`."""
     audios = list(audios)
     _compile_phrases(model, kwargs)              # `phrases` / `phrase_boost`: as in `transcribe`, one list for all files
+    _check_repetition(kwargs)                    # `no_repeat_ngram_size` / `repetition_penalty`: as in `transcribe`
     if in_flight > 1 and len(audios) > 1:
         from .decoding import run_in_lanes
         n = min(int(in_flight), len(audios))
@@ -650,22 +672,24 @@ def _drive_lockstep(model: "Whisper", workers: List[_Transcriber], start, batch_
             groups = {}
             for i in todo:
                 t = workers[i].temperatures[rung[i]]
-                groups.setdefault((_options_key(workers[i].decode_options), id(workers[i].phrases), t), []).append(i)
+                groups.setdefault((_options_key(workers[i].decode_options), id(workers[i].phrases),
+                                   tuple(sorted(workers[i].repetition.items())), t), []).append(i)
             todo = []
-            for (_, _, t), members in groups.items():
+            for (_, _, _, t), members in groups.items():
                 shared = replace(workers[members[0]]._options_for(t), prompt=None)
                 phrases = workers[members[0]].phrases
+                repetition = workers[members[0]].repetition
                 prompts = {i: workers[i].decode_options.get("prompt") for i in members}
-                for chunk in _prompt_batches(model, shared, prompts, members, batch_size, phrases):
+                for chunk in _prompt_batches(model, shared, prompts, members, batch_size, phrases, repetition):
                     # a window on a higher rung has been encoded already: its retry takes the features
                     inputs = [encoded.get(i, pending[i]) for i in chunk]
                     if len({tuple(x.shape) for x in inputs}) > 1:
                         inputs = [pending[i] for i in chunk]
                     if len(chunk) == 1:        # alone: exactly the call `transcribe` makes
-                        decoded = [model.decode(inputs[0], workers[chunk[0]]._options_for(t), **_phrases_kw(phrases))]
+                        decoded = [model.decode(inputs[0], workers[chunk[0]]._options_for(t), **_phrases_kw(phrases), **repetition)]
                     else:
                         decoded = model.decode(torch.stack(inputs), shared, prompts=[prompts[i] for i in chunk],
-                                               **_phrases_kw(phrases))
+                                               **_phrases_kw(phrases), **repetition)
                     for i, result in zip(chunk, decoded):
                         if workers[i]._needs_retry(result) and rung[i] + 1 < len(workers[i].temperatures):
                             rung[i] += 1
@@ -731,7 +755,7 @@ def transcribe_chunked(model: "Whisper", audio: Union[str, np.ndarray, torch.Ten
         above 0.64 (the cut kernel's halo);
       * `verbose=True` prints the segments chunk by chunk in completion order, not in file order; there is no progress bar.
     `device_ingest`: a file path is loaded with `load_audio(path, device=model.device)`, as in `transcribe`; `phrases` /
-    `phrase_boost` likewise.
+    `phrase_boost` and `no_repeat_ngram_size` / `repetition_penalty` likewise.
 
     Returns the dict `transcribe` returns — `segments` concatenated in chunk order with `id` renumbered, `text` the
     concatenation of the chunks' texts, `language` — plus `chunks`: `[(start_s, end_s), ...]`.  A file of at most 30 s has no
@@ -743,6 +767,7 @@ def transcribe_chunked(model: "Whisper", audio: Union[str, np.ndarray, torch.Ten
         raise ValueError(f"batch_size must be at least 1 (got {batch_size})")
     fixed = {k: kwargs.pop(k, default) for k, default in _WALK_DEFAULTS.items()}
     _compile_phrases(model, kwargs)              # `phrases` / `phrase_boost`: as in `transcribe`, one list for all chunks
+    _check_repetition(kwargs)
     if device_ingest and isinstance(audio, str):
         audio = load_audio(audio, device=model.device)
     mel = log_mel_spectrogram(audio, model.dims.n_mels, padding=N_SAMPLES, device=model.device)
