@@ -466,6 +466,23 @@ int wh_task_align_batch(wh_task *t, const int32_t *layers, const int32_t *heads,
                         const int32_t *n_frames, int width, int row_begin, float qk_scale, float *cost_out,
                         int8_t *trace_out, int64_t trace_stride, void *scratch, size_t scratch_bytes, void *stream);
 
+/* Forced alignment of a transcript that may run past the window (no counterpart in the reference):
+ * wh_task_align_batch with an OPEN END on the token axis, followed by the back-trace.  The task has been teacher-forced with the
+ * next candidate tokens of every clip's transcript; the cost matrix and the DTW wavefront are those of wh_task_align_batch (same
+ * tie rule, same trace layout), and in addition the accumulated cost of the last column D[i][M], i = 1..N_r, is kept
+ * (lastcol_out, device fp32 [n_rows][Nmax]).  With m = min_i D[i][M], row r's path leaves the window at
+ *   end[r] = N_r                                                      where closed[r] != 0 (host int32 [n_rows]),
+ *   end[r] = the smallest i with D[i][M] <= m + end_slack * |m|      otherwise (end_slack >= 0; 0 = the first arg-min),
+ * and the walk of wh_dtw_backtrace_batch starts from (end[r], M): end_out device int32 [n_rows], jumps_out device int32
+ * [n_rows][jump_stride] (jump_stride >= Nmax; entries [0, end[r]) are written), path_len_out device int32 [n_rows] (-1: invalid
+ * trace code).  With closed[r] != 0 in every row the results equal wh_task_align_batch + wh_dtw_backtrace_batch.
+ * scratch_bytes >= wh_align_batch_scratch_bytes(...) of the same shape + 8 * n_rows. */
+int wh_task_align_open_batch(wh_task *t, const int32_t *layers, const int32_t *heads, int n_pairs, const int32_t *n_tok,
+                             const int32_t *n_frames, const int32_t *closed, float end_slack, int width, int row_begin,
+                             float qk_scale, float *cost_out, int8_t *trace_out, int64_t trace_stride, float *lastcol_out,
+                             int32_t *end_out, int32_t *jumps_out, int64_t jump_stride, int32_t *path_len_out, void *scratch,
+                             size_t scratch_bytes, void *stream);
+
 /* ---- cutting one long recording at pauses (no counterpart in the reference) ---------------- */
 /* Level of every frame of a log-mel spectrogram as wh_log_mel writes it (values (x + 4) / 4, x = log10 mel power):
  *   L[f] = log10( (1 / n_mels) * sum_m 10^(4 * mel[m][f] - 4) ),  0 <= f < content_frames  (log10 of the mean mel power).

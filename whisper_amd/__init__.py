@@ -20,6 +20,7 @@ from typing import List, Optional, Union
 import torch
 
 from . import audio as _audio
+from .align import align, align_batch
 from .audio import SAMPLE_RATE as _SAMPLE_RATE
 from .audio import log_mel_spectrogram, pad_or_trim
 from .decoding import (DecodingOptions, DecodingResult, ScoreResult, decode, decode_many, detect_language, run_in_lanes,

@@ -1770,6 +1770,58 @@ extern "C" int wh_task_align_batch(wh_task* t, const int32_t* layers, const int3
   return WH_OK;
 }
 
+extern "C" int wh_task_align_open_batch(wh_task* t, const int32_t* layers, const int32_t* heads, int n_pairs,
+                                        const int32_t* n_tok, const int32_t* n_frames, const int32_t* closed, float end_slack,
+                                        int width, int row_begin, float qk_scale, float* cost_out, int8_t* trace_out,
+                                        int64_t trace_stride, float* lastcol_out, int32_t* end_out, int32_t* jumps_out,
+                                        int64_t jump_stride, int32_t* path_len_out, void* scratch, size_t scratch_bytes,
+                                        void* stream_) {
+  TASK_ENTER(t);
+  if (!t || !layers || !heads || !n_tok || !n_frames || !closed || !cost_out || !trace_out || !lastcol_out || !end_out ||
+      !jumps_out || !path_len_out || !scratch || n_pairs <= 0)
+    return WH_ERR_ARG;
+  if (!t->qcap) return WH_ERR_STATE;
+  if (width <= 0 || (width & 1) == 0 || width > 63 || row_begin < 0 || !(end_slack >= 0.f)) return WH_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream_;
+  const wh_dims& d = t->m->d;
+  const int R = t->R, D = d.n_text_state, C = d.n_text_ctx, Ta = d.n_audio_ctx;
+  int Tmax = 0, Fmax = 0;
+  for (int r = 0; r < R; ++r) {
+    if (n_tok[r] <= row_begin + 1 || n_tok[r] > t->pos || n_frames[r] <= 0 || n_frames[r] > Ta) return WH_ERR_ARG;
+    if (n_tok[r] > Tmax) Tmax = n_tok[r];
+    if (n_frames[r] > Fmax) Fmax = n_frames[r];
+  }
+  for (int i = 0; i < n_pairs; ++i)
+    if (layers[i] < 0 || layers[i] >= d.n_text_layer || heads[i] < 0 || heads[i] >= d.n_text_head) return WH_ERR_ARG;
+  const int Nmax = Tmax - 1 - row_begin;
+  if (Nmax > DTW_OPEN_MAX_ROWS) return WH_ERR_LIMIT;
+  if (trace_stride < (int64_t)(Nmax + 1) * (Fmax + 1) || jump_stride < Nmax) return WH_ERR_ARG;
+  float *qk, *w; int* ints;
+  const size_t base_bytes = align_batch_carve(R, n_pairs, Tmax, Ta, Fmax, scratch, &qk, &w, &ints);
+  if (base_bytes + (size_t)2 * R * sizeof(int) > scratch_bytes) return WH_ERR_WORKSPACE;
+  int* ints2 = (int*)((char*)scratch + base_bytes);          // [R] rows of every cost matrix, [R] closed flags
+  std::vector<int> h((size_t)2 * R + 2 * n_pairs), h2((size_t)2 * R);
+  for (int r = 0; r < R; ++r) {
+    h[r] = n_tok[r]; h[R + r] = n_frames[r];
+    h2[r] = n_tok[r] - 1 - row_begin; h2[R + r] = closed[r] != 0;
+  }
+  for (int i = 0; i < n_pairs; ++i) { h[2 * R + i] = layers[i]; h[2 * R + n_pairs + i] = heads[i]; }
+  HIPCHK(hipMemcpyAsync(ints, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(ints2, h2.data(), h2.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));       // `h`, `h2` are host stack memory
+  const int *d_ntok = ints, *d_nfr = ints + R, *d_layers = ints + 2 * R, *d_heads = ints + 2 * R + n_pairs;
+  const int *d_rows = ints2, *d_closed = ints2 + R;
+  HIPCHK(launch_cross_qk_batch(t->qcap, (int64_t)R * C * D, (int64_t)C * D, D, t->cross_kv, (int64_t)t->B * Ta * 2 * D,
+                               (int64_t)Ta * 2 * D, t->G, d_layers, d_heads, n_pairs, d_ntok, R, Tmax, Ta, qk,
+                               t->m->dtype, s));
+  HIPCHK(launch_align_batch(qk, d_ntok, d_nfr, R, n_pairs, Tmax, Ta, Fmax, width, row_begin, 1, qk_scale, cost_out, Nmax, w, s));
+  HIPCHK(launch_dtw_open_batch(cost_out, d_rows, d_nfr, d_closed, R, Nmax, Fmax, end_slack, trace_out, trace_stride,
+                               lastcol_out, end_out, s));
+  HIPCHK(launch_dtw_backtrace_batch(trace_out, trace_stride, end_out, d_nfr, R, Nmax, Fmax, jumps_out, jump_stride, nullptr, 0,
+                                    path_len_out, s));
+  return WH_OK;
+}
+
 extern "C" int wh_median_filter(const float* x, float* out, int64_t rows, int n, int width, void* stream) {
   if (!x || !out || rows < 0 || n <= 0) return WH_ERR_ARG;
   if (width <= 0 || (width & 1) == 0 || width > 63) return WH_ERR_ARG;

@@ -367,6 +367,15 @@ hipError_t launch_align_batch(const float* qk, const int* d_ntok, const int* d_n
 // dtw of every clip's cost matrix; trace of clip b dense [(N_b + 1)][(F_b + 1)] at trace + b * trace_bs
 hipError_t launch_dtw_batch(const float* cost, const int* d_ntok, const int* d_nfr, int clips, int Tmax, int Fmax,
                             int row_begin, int row_tail, int Nmax, int8_t* trace, int64_t trace_bs, hipStream_t stream);
+// open-end dtw: clip b's cost matrix [d_rows[b]][d_cols[b]] (row stride Fmax, slab of Nmax rows); trace as launch_dtw_batch
+// (trace_bs >= (Nmax + 1) * (Fmax + 1)); lastcol [clips][Nmax] = accumulated cost of the last column; end [clips] = the row the
+// path leaves the window at: d_rows[b] where d_closed[b] != 0, else the smallest i with lastcol[i-1] <= m + end_slack * |m|,
+// m the column's minimum; 0 for an empty clip.  Pass `end` to launch_dtw_backtrace_batch as its row counts.
+// Nmax <= DTW_OPEN_MAX_ROWS: the wavefront keeps three diagonals of Nmax + 1 floats in 64 KB of LDS.
+constexpr int DTW_OPEN_MAX_ROWS = 5460;
+hipError_t launch_dtw_open_batch(const float* cost, const int* d_rows, const int* d_cols, const int* d_closed, int clips,
+                                 int Nmax, int Fmax, float end_slack, int8_t* trace, int64_t trace_bs, float* lastcol,
+                                 int* end, hipStream_t stream);
 // back-trace of every clip's trace (dense [(rows_b + 1)][(cols_b + 1)] at trace + b * trace_bs; d_rows / d_cols device
 // arrays): jumps [clips][jump_stride] = frame at which each text index is first reached; optional right-aligned path
 // [clips][2][path_stride] + path_len [clips]

@@ -172,4 +172,19 @@ int wht_phrase_root_table(const int* child_begin, const int* child_token, const 
   return launch_phrase_root_table(child_begin, child_token, child_node, n_edges, V, root, (hipStream_t)stream);
 }
 
+// open-end dtw, end selection and back-trace (timing.hip) on caller-supplied cost matrices [clips][Nmax][Fmax]; d_rows /
+// d_cols / d_closed device int [clips]; path (optional) as launch_dtw_backtrace_batch lays it out
+int wht_dtw_open(const float* cost, const int* d_rows, const int* d_cols, const int* d_closed, int clips, int Nmax, int Fmax,
+                 float end_slack, int8_t* trace, int64_t trace_bs, float* lastcol, int* end, int* jumps, int64_t jump_stride,
+                 int* path, int64_t path_stride, int* path_len, void* stream) {
+  if (!cost || !d_rows || !d_cols || !d_closed || !trace || !lastcol || !end || !jumps || !path_len || jump_stride < Nmax ||
+      (path && path_stride < (int64_t)Nmax + Fmax))
+    return hipErrorInvalidValue;
+  const hipError_t e = launch_dtw_open_batch(cost, d_rows, d_cols, d_closed, clips, Nmax, Fmax, end_slack, trace, trace_bs,
+                                             lastcol, end, (hipStream_t)stream);
+  if (e != hipSuccess) return e;
+  return launch_dtw_backtrace_batch(trace, trace_bs, end, d_cols, clips, Nmax, Fmax, jumps, jump_stride, path, path_stride,
+                                    path_len, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -263,6 +263,91 @@ __global__ __launch_bounds__(1024) void dtw_batch_kernel(const float* __restrict
   }
 }
 
+// ---- open-end dtw (forced alignment of a transcript that runs past the window) ---------------------------------------------
+// dtw_batch_kernel's sibling: the same wavefront, tie rule and trace layout over clip b's cost matrix [n_rows[b]][n_cols[b]]
+// (rows of stride ldx inside a slab of Nmax rows), and in addition the accumulated cost of the LAST COLUMN,
+// lastcol[b][i - 1] = D[i][M] for i = 1..N, stored when cell (i, M) is computed on diagonal k = i + M.  Every cell is one
+// fp32 add of x + min(three): a float32 restatement on the host gives the same bits.
+__global__ __launch_bounds__(1024) void dtw_open_batch_kernel(const float* __restrict__ x, const int* __restrict__ n_rows,
+                                                              const int* __restrict__ n_cols, int Nmax, int64_t ldx,
+                                                              int8_t* __restrict__ trace_all, int64_t trace_bs,
+                                                              float* __restrict__ lastcol_all) {
+  extern __shared__ float diag[];          // 3 x (Nmax+1)
+  const int b = blockIdx.x;
+  const int N = n_rows[b], M = n_cols[b];
+  if (N <= 0 || M <= 0 || N > Nmax || M > ldx) return;
+  const float* xb = x + (int64_t)b * Nmax * ldx;
+  int8_t* trace = trace_all + b * trace_bs;
+  float* lastcol = lastcol_all + (int64_t)b * Nmax;
+  float* d[3] = {diag, diag + (Nmax + 1), diag + 2 * (Nmax + 1)};
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int j = tid + 1; j <= M; j += nt) trace[j] = 2;
+  for (int i = tid; i <= N; i += nt) trace[(int64_t)i * (M + 1)] = 1;
+  for (int i = tid; i <= N; i += nt) {
+    d[0][i] = (i == 0) ? 0.f : __builtin_huge_valf();
+    d[1][i] = __builtin_huge_valf();
+  }
+  __syncthreads();
+  for (int k = 2; k <= N + M; ++k) {
+    float* d2 = d[(k - 2) % 3];
+    float* d1 = d[(k - 1) % 3];
+    float* d0 = d[k % 3];
+    for (int i = tid + 1; i <= N; i += nt) {
+      const int j = k - i;
+      float c = __builtin_huge_valf();
+      if (j >= 1 && j <= M) {
+        const float c0 = d2[i - 1], c1 = d1[i - 1], c2 = d1[i];
+        float cm; int8_t t;
+        if (c0 < c1 && c0 < c2) { cm = c0; t = 0; }
+        else if (c1 < c0 && c1 < c2) { cm = c1; t = 1; }
+        else { cm = c2; t = 2; }
+        c = xb[(int64_t)(i - 1) * ldx + (j - 1)] + cm;
+        trace[(int64_t)i * (M + 1) + j] = t;
+        if (j == M) lastcol[i - 1] = c;
+      }
+      d0[i] = c;
+    }
+    if (tid == 0) d0[0] = __builtin_huge_valf();
+    __syncthreads();
+  }
+}
+
+// where the path of every clip leaves its window: end[b] = the row the back-trace starts from.  m = min_i D[i][M]; a closed
+// clip (the transcript ends inside the window) takes N; any other the SMALLEST i with D[i][M] <= m + end_slack * |m| — past
+// the last spoken token the last column is a plateau on which the plain arg-min is decided by noise.  One workgroup per clip,
+// two LDS reductions (min of the values, then min of the qualifying rows); products and sums rounded separately, as numpy's.
+__global__ __launch_bounds__(256) void dtw_open_select_kernel(const float* __restrict__ lastcol_all, const int* __restrict__ n_rows,
+                                                              const int* __restrict__ n_cols, const int* __restrict__ closed,
+                                                              int Nmax, int Fmax, float end_slack, int* __restrict__ end) {
+  __shared__ float redf[256];
+  __shared__ int redi[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int N = n_rows[b], M = n_cols[b];
+  if (N <= 0 || M <= 0 || N > Nmax || M > Fmax) { if (tid == 0) end[b] = 0; return; }       // workgroup-uniform
+  if (closed[b] != 0) { if (tid == 0) end[b] = N; return; }
+  const float* lastcol = lastcol_all + (int64_t)b * Nmax;
+  float m = __builtin_huge_valf();
+  for (int i = tid; i < N; i += 256) m = fminf(m, lastcol[i]);
+  redf[tid] = m;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) redf[tid] = fminf(redf[tid], redf[tid + s]);
+    __syncthreads();
+  }
+  m = redf[0];
+  const float bound = __fadd_rn(m, __fmul_rn(end_slack, fabsf(m)));
+  // finite costs: the arg-min row itself qualifies.  m = -inf or NaN makes `bound` NaN and no row qualifies: all N rows
+  int first = N;
+  for (int i = tid; i < N; i += 256)
+    if (lastcol[i] <= bound) { first = i + 1; break; }
+  redi[tid] = first;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) redi[tid] = min(redi[tid], redi[tid + s]);
+    __syncthreads();
+  }
+  if (tid == 0) end[b] = redi[0];
+}
 
 // ---- back-trace of every clip's trace matrix on the device (timing.py:57-79) ------------------------------------------
 // One workgroup per clip.  The clip's int8 trace [(N+1)][(M+1)] is first packed to 2 bits per entry in LDS by all
@@ -367,6 +452,24 @@ hipError_t launch_dtw_batch(const float* cost, const int* d_ntok, const int* d_n
   if (threads > 1024) threads = 1024;
   const size_t lds = 3 * (size_t)(Nmax + 1) * sizeof(float);
   hipLaunchKernelGGL(dtw_batch_kernel, dim3(clips), dim3(threads), lds, stream, cost, ab, row_begin, row_tail, Nmax, trace, trace_bs);
+  return hipGetLastError();
+}
+
+hipError_t launch_dtw_open_batch(const float* cost, const int* d_rows, const int* d_cols, const int* d_closed, int clips,
+                                 int Nmax, int Fmax, float end_slack, int8_t* trace, int64_t trace_bs, float* lastcol,
+                                 int* end, hipStream_t stream) {
+  if (clips <= 0) return hipSuccess;
+  // three diagonals of Nmax + 1 floats have to fit the 64 KB of dynamic LDS a kernel gets without asking for more
+  if (Nmax <= 0 || Nmax > DTW_OPEN_MAX_ROWS || Fmax <= 0 || !(end_slack >= 0.f)) return hipErrorInvalidValue;
+  if (trace_bs < (int64_t)(Nmax + 1) * (Fmax + 1)) return hipErrorInvalidValue;
+  int threads = ((Nmax + 63) / 64) * 64;
+  if (threads > 1024) threads = 1024;
+  const size_t lds = 3 * (size_t)(Nmax + 1) * sizeof(float);
+  static_assert(3 * (size_t)(DTW_OPEN_MAX_ROWS + 1) * sizeof(float) <= 64 * 1024, "dtw_open_batch_kernel: LDS");
+  hipLaunchKernelGGL(dtw_open_batch_kernel, dim3(clips), dim3(threads), lds, stream, cost, d_rows, d_cols, Nmax, (int64_t)Fmax,
+                     trace, trace_bs, lastcol);
+  hipLaunchKernelGGL(dtw_open_select_kernel, dim3(clips), dim3(256), 0, stream, lastcol, d_rows, d_cols, d_closed, Nmax, Fmax,
+                     end_slack, end);
   return hipGetLastError();
 }
 

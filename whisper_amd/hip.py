@@ -142,6 +142,10 @@ SIGNATURES = {
     "wh_task_align_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int64,
                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wh_task_align_open_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float, C.c_int, C.c_int, C.c_float,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "wh_median_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "wh_dtw_trace": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "wh_dtw_backtrace_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
@@ -968,6 +972,42 @@ class HipTask:
             t_.record_stream(self.stream)
         return cost, jumps, plen
 
+    def align_open_batch(self, layers: Sequence[int], heads: Sequence[int], n_tok: Sequence[int], n_frames: Sequence[int],
+                         closed: Sequence[int], end_slack: float, width: int, row_begin: int, qk_scale: float = 1.0):
+        """align_batch with an open end on the token axis (wh_task_align_open_batch): every row has been teacher-forced with
+        the NEXT candidate tokens of its transcript, and the DTW decides how many of them lie inside the window.  Returns
+        (cost [R][Nmax][Fmax] fp32, lastcol [R][Nmax] fp32, end int32 [R], jumps int32 [R][Nmax], path_len int32 [R], all on
+        the device): end[r] = the cost-matrix row the path of clip r leaves the window at (all of them where closed[r]),
+        jumps[r][i] for i < end[r] as align_batch's.  Nothing is copied to the host here."""
+        R, P = self.n_rows, len(layers)
+        assert len(n_tok) == R and len(n_frames) == R and len(closed) == R
+        Tmax, Fmax = max(n_tok), max(n_frames)
+        Nmax = Tmax - 1 - row_begin
+        dev = self.model.device
+        need = lib().wh_align_batch_scratch_bytes(R, P, Tmax, self.model.dims.n_audio_ctx, Fmax) + 8 * R
+        scratch = getattr(self, "_align_scratch", None)          # the task's own slabs, as in align_batch
+        if scratch is None or scratch.numel() < need:
+            self._align_scratch = None
+            scratch = self._align_scratch = self.model._alloc(int(need))
+            scratch.record_stream(self.stream)
+        cost = torch.empty(R, Nmax, Fmax, dtype=torch.float32, device=dev)
+        stride = (Nmax + 1) * (Fmax + 1)
+        trace = torch.empty(R, stride, dtype=torch.int8, device=dev)
+        lastcol = torch.zeros(R, Nmax, dtype=torch.float32, device=dev)
+        end = torch.zeros(R, dtype=torch.int32, device=dev)
+        jumps = torch.zeros(R, Nmax, dtype=torch.int32, device=dev)
+        plen = torch.zeros(R, dtype=torch.int32, device=dev)
+        arr = lambda v: (C.c_int32 * len(v))(*[int(x) for x in v])
+        with self._call():
+            check(lib().wh_task_align_open_batch(self.handle, arr(layers), arr(heads), P, arr(n_tok), arr(n_frames), arr(closed),
+                                                 float(end_slack), width, row_begin, float(qk_scale), cost.data_ptr(),
+                                                 trace.data_ptr(), stride, lastcol.data_ptr(), end.data_ptr(), jumps.data_ptr(),
+                                                 Nmax, plen.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                 stream_ptr(self.stream)), "wh_task_align_open_batch")
+        for t_ in (cost, trace, lastcol, end, jumps, plen):
+            t_.record_stream(self.stream)
+        return cost, lastcol, end, jumps, plen
+
 
 class PendingLoop:
     """A fused greedy / beam loop that has been begun (`HipTask.greedy_begin` / `beam_begin`).  `poll()` queues further
@@ -1117,6 +1157,60 @@ def dtw_backtrace(trace: torch.Tensor, want_path: bool = True):
     if not want_path:
         return jumps, None
     return jumps, path[:, N + M - n:]
+
+
+_KTEST_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwhisper_hip_ktest.so")
+_KTEST = None
+# the test-only library's entry points bound here (csrc/ktest.cpp; the others are bound by the tests that use them)
+KTEST_SIGNATURES = {
+    "wht_dtw_open": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                               C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                               C.c_void_p]),
+}
+
+
+def ktest_lib():
+    """libwhisper_hip_ktest.so: flat test entry points over the shipped kernel launchers, built with the library"""
+    global _KTEST
+    if _KTEST is None:
+        if not os.path.isfile(_KTEST_PATH):
+            raise HipError(f"{_KTEST_PATH} is missing: build it with `make -C whisper_amd/csrc`")
+        handle = C.CDLL(_KTEST_PATH)
+        for name, (res, args) in KTEST_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
+        _KTEST = handle
+    return _KTEST
+
+
+def dtw_open_ktest(cost: torch.Tensor, n_rows: Sequence[int], n_cols: Sequence[int], closed: Sequence[int], end_slack: float):
+    """Open-end DTW, end selection and back-trace on caller-supplied cost matrices, without a model (wht_dtw_open):
+    cost fp32 [clips][Nmax][Fmax] on the GPU, clip b using its first n_rows[b] x n_cols[b] entries.  Returns device tensors
+    (trace int8 [clips][(Nmax+1)*(Fmax+1)], lastcol fp32 [clips][Nmax], end int32 [clips], jumps int32 [clips][Nmax],
+    path int32 [clips][2][Nmax+Fmax] right-aligned, path_len int32 [clips])."""
+    require_gpu(cost.device)
+    assert cost.dtype == torch.float32 and cost.dim() == 3 and cost.is_contiguous()
+    clips, Nmax, Fmax = cost.shape
+    assert len(n_rows) == clips and len(n_cols) == clips and len(closed) == clips
+    assert all(0 <= int(n) <= Nmax for n in n_rows) and all(0 <= int(m) <= Fmax for m in n_cols)
+    dev = cost.device
+    sizes = torch.tensor([[int(x) for x in n_rows], [int(x) for x in n_cols], [int(bool(x)) for x in closed]],
+                         dtype=torch.int32).to(dev)
+    stride = (Nmax + 1) * (Fmax + 1)
+    trace = torch.full((clips, stride), -1, dtype=torch.int8, device=dev)
+    lastcol = torch.zeros(clips, Nmax, dtype=torch.float32, device=dev)
+    end = torch.full((clips,), -1, dtype=torch.int32, device=dev)
+    jumps = torch.zeros(clips, Nmax, dtype=torch.int32, device=dev)
+    path = torch.zeros(clips, 2, Nmax + Fmax, dtype=torch.int32, device=dev)
+    plen = torch.zeros(clips, dtype=torch.int32, device=dev)
+    s = torch.cuda.current_stream(dev)
+    rc = ktest_lib().wht_dtw_open(cost.data_ptr(), sizes[0].data_ptr(), sizes[1].data_ptr(), sizes[2].data_ptr(), clips, Nmax,
+                                  Fmax, float(end_slack), trace.data_ptr(), stride, lastcol.data_ptr(), end.data_ptr(),
+                                  jumps.data_ptr(), Nmax, path.data_ptr(), Nmax + Fmax, plen.data_ptr(), stream_ptr(s))
+    if rc != 0:
+        raise HipError(f"wht_dtw_open: hipError {rc}")
+    return trace, lastcol, end, jumps, path, plen
 
 
 def align_matrix(qk: torch.Tensor, n_frames: int, width: int, row_begin: int, row_end: int,

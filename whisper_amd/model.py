@@ -28,6 +28,8 @@ from torch import Tensor
 from . import hip
 from .decoding import decode as decode_function
 from .decoding import detect_language as detect_language_function
+from .align import align as align_function
+from .align import align_batch as align_batch_function
 from .transcribe import transcribe as transcribe_function
 from .transcribe import transcribe_batch as transcribe_batch_function
 from .transcribe import transcribe_chunked as transcribe_chunked_function
@@ -385,4 +387,6 @@ class Whisper:
     transcribe = transcribe_function
     transcribe_batch = transcribe_batch_function     # extension: lock-step batching over files
     transcribe_chunked = transcribe_chunked_function   # extension: one long file cut at pauses, chunks decoded batched
+    align = align_function                             # extension: word times for a transcript the caller already has
+    align_batch = align_batch_function
     decode = decode_function

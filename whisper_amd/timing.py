@@ -158,6 +158,34 @@ def find_alignment_batch(model: "Whisper", tokenizer: Tokenizer, text_tokens: Li
     live = [i for i in range(B) if len(text_tokens[i]) > 0]
     if not live:
         return out
+    run = lambda task, heads, n_tok, frames, ids, n_sot: task.align_batch([h[0] for h in heads], [h[1] for h in heads], n_tok,
+                                                                         frames, medfilt_width, n_sot, qk_scale)
+    for ids, (cost, jumps, plen), probs in _teacher_forced_chunks(model, tokenizer, text_tokens, live, mel, num_frames,
+                                                                  audio_features, run):
+        # ONE copy to the host (the paths' jump frames and the probabilities: a few KB per clip — the trace matrices stay
+        # on the device)
+        jumps_h, probs_h = jumps.cpu().numpy(), probs.cpu().numpy()
+        if bool((plen.cpu() < 0).any()):
+            raise ValueError("Unexpected trace[i, j]")          # reference timing.py:77
+        if stats is not None:
+            stats["device_s"] = stats.get("device_s", 0.0) + time.perf_counter() - t_start
+            t_start = time.perf_counter()
+        for k, i in enumerate(ids):
+            tt = list(text_tokens[i])
+            out[i] = _words_from_jumps(tokenizer, tt, probs_h[k, : len(tt)].tolist(), jumps_h[k, : len(tt) + 1])
+        if stats is not None:
+            stats["host_s"] = stats.get("host_s", 0.0) + time.perf_counter() - t_start
+            t_start = time.perf_counter()
+    return out
+
+
+def _teacher_forced_chunks(model: "Whisper", tokenizer: Tokenizer, text_tokens: List[List[int]], live: List[int],
+                           mel: Optional[torch.Tensor], num_frames: List[int], audio_features: Optional[torch.Tensor], run):
+    """The part find_alignment_batch and find_alignment_open_batch share: the clips `live` in chunks whose fp32 score slabs
+    stay bounded, each chunk one encoder pass (none with `audio_features`), one teacher-forced prefill of
+    [sot, <|notimestamps|>, text, eot] per clip (rows padded on the right) and `run(task, heads, n_tok, frames, ids, n_sot)`
+    — the alignment call on the task — then the probabilities of all text tokens in one gather.
+    Yields (ids, what `run` returned, probs (clips, n_text_max)) per chunk, everything on the device."""
     n_sot = len(tokenizer.sot_sequence)
     heads = model.alignment_heads.indices().T.tolist()
     dims = model.dims
@@ -165,9 +193,9 @@ def find_alignment_batch(model: "Whisper", tokenizer: Tokenizer, text_tokens: Li
     tmax_all = max(len(text_tokens[i]) for i in live) + n_sot + 2
     per_clip = len(heads) * tmax_all * (dims.n_audio_ctx + 2 * (max(num_frames) // 2)) * 4
     chunk = max(1, min(len(live), ALIGN_BATCH_SCRATCH_BYTES // max(per_clip, 1)))
-    with torch.no_grad():
-        for c0 in range(0, len(live), chunk):
-            ids = live[c0: c0 + chunk]
+    for c0 in range(0, len(live), chunk):
+        ids = live[c0: c0 + chunk]
+        with torch.no_grad():                 # per chunk, closed before the yield: never held while the consumer runs
             rows = [[*tokenizer.sot_sequence, tokenizer.no_timestamps, *text_tokens[i], tokenizer.eot] for i in ids]
             n_tok = [len(r) for r in rows]
             Tmax = max(n_tok)
@@ -179,28 +207,74 @@ def find_alignment_batch(model: "Whisper", tokenizer: Tokenizer, text_tokens: Li
                 task.set_audio(features.contiguous())
                 n_text_max = Tmax - n_sot - 2
                 logits = task.prefill(tokens.contiguous(), sel=list(range(n_sot, n_sot + n_text_max)))   # (rows, n_text_max, V)
-                cost, jumps, plen = task.align_batch([h[0] for h in heads], [h[1] for h in heads], n_tok,
-                                               [int(num_frames[i]) // 2 for i in ids], medfilt_width, n_sot, qk_scale)
+                aligned = run(task, heads, n_tok, [int(num_frames[i]) // 2 for i in ids], ids, n_sot)
             finally:
                 task.close()
-            # probabilities of all text tokens of all clips in one gather; ONE copy to the host (the paths' jump frames
-            # and the probabilities: a few KB per clip — the trace matrices stay on the device)
             padded = torch.tensor([list(text_tokens[i]) + [0] * (n_text_max - len(text_tokens[i])) for i in ids],
                                   device=model.device)
             probs = _token_probs(logits, padded, tokenizer.eot)
-            jumps_h, probs_h = jumps.cpu().numpy(), probs.cpu().numpy()
-            if bool((plen.cpu() < 0).any()):
-                raise ValueError("Unexpected trace[i, j]")          # reference timing.py:77
-            if stats is not None:
-                stats["device_s"] = stats.get("device_s", 0.0) + time.perf_counter() - t_start
-                t_start = time.perf_counter()
-            for k, i in enumerate(ids):
-                tt = list(text_tokens[i])
-                out[i] = _words_from_jumps(tokenizer, tt, probs_h[k, : len(tt)].tolist(), jumps_h[k, : len(tt) + 1])
-            if stats is not None:
-                stats["host_s"] = stats.get("host_s", 0.0) + time.perf_counter() - t_start
-                t_start = time.perf_counter()
+        yield ids, aligned, probs
+
+
+def find_alignment_open_batch(model: "Whisper", tokenizer: Tokenizer, text_tokens: List[List[int]], mel: Optional[torch.Tensor],
+                              num_frames: List[int], closed: List[bool], *, end_slack: float = 0.01, medfilt_width: int = 7,
+                              qk_scale: float = 1.0, audio_features: Optional[torch.Tensor] = None,
+                              details: Optional[list] = None):
+    """`find_alignment_batch` for token lists that may run PAST their windows (no counterpart in the reference): clip i is
+    teacher-forced with `text_tokens[i]` — the next candidate tokens of a transcript the caller already has — and an
+    open-end DTW decides how many of them are spoken inside its `num_frames[i]` mel frames, and where
+    (wh_task_align_open_batch: the last column's accumulated cost, the end row — all rows where `closed[i]`, else the
+    smallest row within `end_slack` of the column's minimum — and the back-trace from there, all on the device).
+    Returns one `(words, n_tokens)` per clip: the WordTimings of the words whose tokens — and the row that ends them — all
+    lie in front of the end row, and the number of text tokens they cover.  A closed clip returns what
+    `find_alignment_batch` returns.  `details` (list, optional) receives per clip a dict with the device's own "cost"
+    (rows x frames), "lastcol", "end" and "jumps" as numpy arrays (None for a clip without tokens)."""
+    B = len(text_tokens)
+    if not (len(num_frames) == B and len(closed) == B):
+        raise ValueError("text_tokens, num_frames and closed must have one entry per clip")
+    if not end_slack >= 0.0:
+        raise ValueError(f"end_slack must be >= 0 (got {end_slack})")
+    out = [([], 0) for _ in range(B)]
+    if details is not None:
+        details.clear()
+        details.extend([None] * B)
+    live = [i for i in range(B) if len(text_tokens[i]) > 0]
+    if not live:
+        return out
+    if max(len(text_tokens[i]) for i in live) + len(tokenizer.sot_sequence) + 2 > model.dims.n_text_ctx:
+        raise ValueError(f"{max(len(text_tokens[i]) for i in live)} candidate tokens do not fit the decoder's context")
+    run = lambda task, heads, n_tok, frames, ids, n_sot: task.align_open_batch(
+        [h[0] for h in heads], [h[1] for h in heads], n_tok, frames, [int(bool(closed[i])) for i in ids], end_slack,
+        medfilt_width, n_sot, qk_scale)
+    for ids, (cost, lastcol, end, jumps, plen), probs in _teacher_forced_chunks(model, tokenizer, text_tokens, live, mel,
+                                                                                num_frames, audio_features, run):
+        jumps_h, probs_h, end_h = jumps.cpu().numpy(), probs.cpu().numpy(), end.cpu().numpy()
+        if bool((plen.cpu() < 0).any()):
+            raise ValueError("Unexpected trace[i, j]")
+        if details is not None:
+            cost_h, lastcol_h = cost.cpu().numpy(), lastcol.cpu().numpy()
+        for k, i in enumerate(ids):
+            tt = list(text_tokens[i])
+            e = int(end_h[k])
+            if details is not None:
+                details[i] = dict(cost=cost_h[k, : len(tt) + 1, : int(num_frames[i]) // 2].copy(),
+                                  lastcol=lastcol_h[k, : len(tt) + 1].copy(), end=e, jumps=jumps_h[k, :e].copy())
+            out[i] = _words_in_front_of(tokenizer, tt, probs_h[k, : len(tt)].tolist(), jumps_h[k, :e])
     return out
+
+
+def _words_in_front_of(tokenizer: Tokenizer, text_tokens: List[int], text_token_probs: List[float], jump_frames: np.ndarray):
+    """`_words_from_jumps` for a path that ends at row len(jump_frames): word k spans rows [b_k, b_{k+1}) and ends where row
+    b_{k+1} begins, so it is kept while b_{k+1} < len(jump_frames).  Returns (words, tokens covered)."""
+    words, word_tokens = tokenizer.split_to_word_tokens(text_tokens + [tokenizer.eot])
+    bounds = np.pad(np.cumsum([len(t) for t in word_tokens[:-1]]), (1, 0))
+    keep = int(np.searchsorted(bounds, len(jump_frames), side="left")) - 1     # boundaries b with b <= end - 1, minus b_0
+    if keep <= 0:
+        return [], 0
+    jump_times = np.asarray(jump_frames) / TOKENS_PER_SECOND
+    out = [WordTiming(words[k], word_tokens[k], float(jump_times[bounds[k]]), float(jump_times[bounds[k + 1]]),
+                      float(np.mean(text_token_probs[bounds[k]: bounds[k + 1]]))) for k in range(keep)]
+    return out, int(bounds[keep])
 
 
 def merge_punctuations(alignment: List[WordTiming], prepended: str, appended: str):
