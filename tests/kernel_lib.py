@@ -28,6 +28,11 @@ SIGNATURES = {
     "wht_gather_cache": (_I, [_P, _P, _P, _I, _L, _L, _P]),
     "wht_permute_groups": (_I, [_P, _P, _I, _L, _I, _I, _L, _L, _P, _P, _L, _P]),
     "wht_replicate_row": (_I, [_P, _L, _I, _L, _I, _I, _I, _L, _P]),
+    "wht_beam_kmax": (_I, []),
+    "wht_beam_scratch_bytes": (ctypes.c_size_t, [_I, _I]),
+    "wht_beam_cand_offsets": (None, [_I, _I, ctypes.POINTER(_L), ctypes.POINTER(_L)]),
+    "wht_beam_step": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P,
+                           ctypes.c_size_t, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

@@ -172,6 +172,41 @@ int wht_phrase_root_table(const int* child_begin, const int* child_token, const 
   return launch_phrase_root_table(child_begin, child_token, child_node, n_edges, V, root, (hipStream_t)stream);
 }
 
+// one beam-search update (beam.hip): the three launches of launch_beam_step on caller-supplied buffers.  B, G, K and R
+// are independent so that the launcher's own refusals can be reached; lag, lcp / copy_from and suppress_mask may be NULL.
+// `scratch` (wht_beam_scratch_bytes(R, V) bytes) is carved with beam_scratch_carve; wht_beam_cand_offsets gives the byte
+// offsets of cand_lp / cand_tok ([R][BEAM_KMAX] each) inside it, so a test reads the candidates the update kernel saw.
+int wht_beam_kmax() { return BEAM_KMAX; }
+size_t wht_beam_scratch_bytes(int R, int V) { return beam_scratch_bytes(R, V); }
+void wht_beam_cand_offsets(int R, int V, int64_t* lp_off, int64_t* tok_off) {
+  BeamArgs a;
+  memset(&a, 0, sizeof a);
+  const uintptr_t base = 4096;
+  beam_scratch_carve(a, (void*)base, R, V);
+  *lp_off = (int64_t)((uintptr_t)a.cand_lp - base);
+  *tok_off = (int64_t)((uintptr_t)a.cand_tok - base);
+}
+int wht_beam_step(const float* logits, int64_t logits_ld, int B, int G, int K, int R, int V, const int64_t* tokens_in,
+                  int64_t* tokens_out, int64_t token_stride, const int* d_ntok, const int* lag, int sample_begin, int eot,
+                  int timestamp_begin, int no_timestamps, int max_initial_ts, int suppress_blank, int blank_token,
+                  const uint8_t* suppress_mask, float* sum_logprobs, void* scratch, size_t scratch_bytes, int64_t* fin_tok,
+                  int* fin_len, float* fin_score, int* fin_count, int max_candidates, int* src, int* lcp, int* copy_from,
+                  int64_t* step_tokens, const int* done_prev, int* done_next, int* d_applied, int first, void* stream) {
+  if (R < 1 || V < 1 || !scratch || scratch_bytes < beam_scratch_bytes(R, V)) return hipErrorInvalidValue;
+  BeamArgs a;
+  memset(&a, 0, sizeof a);
+  a.logits = logits; a.logits_ld = logits_ld; a.R = R; a.V = V; a.G = G; a.K = K;
+  a.tokens_in = tokens_in; a.tokens_out = tokens_out; a.token_stride = token_stride; a.d_ntok = d_ntok; a.lag = lag;
+  a.sample_begin = sample_begin; a.eot = eot; a.timestamp_begin = timestamp_begin; a.no_timestamps = no_timestamps;
+  a.max_initial_ts = max_initial_ts; a.suppress_blank = suppress_blank; a.blank_token = blank_token;
+  a.suppress_mask = suppress_mask; a.sum_logprobs = sum_logprobs;
+  beam_scratch_carve(a, scratch, R, V);
+  a.fin_tok = fin_tok; a.fin_len = fin_len; a.fin_score = fin_score; a.fin_count = fin_count;
+  a.max_candidates = max_candidates; a.src = src; a.lcp = lcp; a.copy_from = copy_from; a.step_tokens = step_tokens;
+  a.done_prev = done_prev; a.done_next = done_next; a.d_applied = d_applied; a.first = first;
+  return launch_beam_step(a, B, (hipStream_t)stream);
+}
+
 // open-end dtw, end selection and back-trace (timing.hip) on caller-supplied cost matrices [clips][Nmax][Fmax]; d_rows /
 // d_cols / d_closed device int [clips]; path (optional) as launch_dtw_backtrace_batch lays it out
 int wht_dtw_open(const float* cost, const int* d_rows, const int* d_cols, const int* d_closed, int clips, int Nmax, int Fmax,
