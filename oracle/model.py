@@ -27,8 +27,9 @@ class OracleModel:
         self.sd = {k: v.detach().cpu().float() for k, v in sd.items()}
 
     # -- primitives -----------------------------------------------------------------------------
-    def _ln(self, x, p):      # model.py:39-41
-        return F.layer_norm(x.float(), (x.shape[-1],), self.sd[p + ".weight"], self.sd[p + ".bias"], 1e-5).to(x.dtype)
+    def _ln(self, x, p):      # model.py:39-41 (float64 activations — the kernel tests' references — stay float64)
+        t = torch.float64 if x.dtype == torch.float64 else torch.float32
+        return F.layer_norm(x.to(t), (x.shape[-1],), self.sd[p + ".weight"].to(t), self.sd[p + ".bias"].to(t), 1e-5).to(x.dtype)
 
     def _lin(self, x, p):     # model.py:44-50
         b = self.sd.get(p + ".bias")
@@ -51,7 +52,7 @@ class OracleModel:
             Tk = k.shape[1]
             mask = torch.full((Tq, Tk), -np.inf).triu_(1 + causal_offset)
             qk = qk + mask
-        qk = qk.float()
+        qk = qk if qk.dtype == torch.float64 else qk.float()
         w = F.softmax(qk, dim=-1).to(q.dtype)
         return (w @ vh).permute(0, 2, 1, 3).flatten(start_dim=2), qk
 

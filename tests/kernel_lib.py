@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(ROOT, "whisper_amd", "libwhisper_hip_ktest.so")
 
 hipSuccess = 0
 hipErrorInvalidValue = 1
+hipErrorNotSupported = 801
 
 _P, _I, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
 SIGNATURES = {
@@ -28,6 +29,12 @@ SIGNATURES = {
     "wht_gather_cache": (_I, [_P, _P, _P, _I, _L, _L, _P]),
     "wht_permute_groups": (_I, [_P, _P, _I, _L, _I, _I, _L, _L, _P, _P, _L, _P]),
     "wht_replicate_row": (_I, [_P, _L, _I, _L, _I, _I, _I, _L, _P]),
+    "wht_xattn_supported": (_I, [_I, _I, _I, _I, _I, _I]),
+    "wht_sattn_supported": (_I, [_I, _I, _I, _I]),
+    "wht_fused_mode": (_I, [_I]),
+    "wht_xattn8": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _L, _L, _P, _L, _L, _I, _I, _P, _L, _P, _P, _P, _P, _I, _I, _P, _I,
+                        _P, _P]),
+    "wht_sattn8": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P, _L, _P, _P, _I, _I, _P, _I, _P, _P]),
     "wht_beam_kmax": (_I, []),
     "wht_beam_scratch_bytes": (ctypes.c_size_t, [_I, _I]),
     "wht_beam_cand_offsets": (None, [_I, _I, ctypes.POINTER(_L), ctypes.POINTER(_L)]),

@@ -36,95 +36,16 @@ import pytest
 import torch
 
 from kernel_lib import hipErrorInvalidValue, hipSuccess, last_form, lib
+from parity_ref import (C_ATT_MFMA, C_ATT_VALU, C_DOT, F16, F32, GUARD, Buf, _dev, _flip_slack, _merge_ref,  # noqa: F401
+                        _r, _stream, _tdt, _ulp, attn_bound, attn_ref, ln_rows_ref)
 
 pytestmark = pytest.mark.gpu
 
-F16, F32 = 1, 0
 PLAIN, LN, COMBINE = 0, 1, 2
 STORE, QKV, RESID, GELU, EPI_F32 = 0, 1, 2, 3, 4
-C_DOT = 2.0 ** -20
-# attention: C_ATT * (sum p |v| / sum p).  The VALU forms keep p in fp32; the MFMA forms (beam-group diag / mfma, flash)
-# round p to fp16 before the P.V product (2^-11 relative), and flash's unscaled form sums l from the fp32 p
-C_ATT_VALU = 2.0 ** -20
-C_ATT_MFMA = 2.0 ** -10
-GUARD = 4096                 # guard bytes in front of and behind every buffer
 
 REPORT = {}                  # form -> largest error / bound ratio
 FORMS = set()                # every form tag seen
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _tdt(dtype):
-    return torch.float16 if dtype == F16 else torch.float32
-
-
-class Buf:
-    """A device buffer of `n` elements inside 0xFF guard bytes; `.t` is the payload view, `.raw` the whole allocation."""
-
-    def __init__(self, n, tdt):
-        es = torch.empty((), dtype=tdt).element_size()
-        self.g = GUARD // es
-        self.raw = torch.full((n + 2 * self.g,), 0, dtype=tdt, device=_dev())
-        self.raw.view(torch.uint8).fill_(0xFF)
-        self.t = self.raw[self.g:self.g + n]
-        self.snap = None
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def snapshot(self):
-        self.snap = self.raw.view(torch.uint8).clone()
-
-    def changed(self):
-        """byte mask (payload elements) of what differs from the snapshot; guard bytes must be untouched."""
-        now = self.raw.view(torch.uint8)
-        diff = now != self.snap
-        es = self.raw.element_size()
-        gb = self.g * es
-        assert not diff[:gb].any() and not diff[len(diff) - gb:].any(), "write outside the allocation's payload"
-        return diff[gb:len(diff) - gb].view(-1, es).any(1)
-
-
-def _ulp(x, dtype):
-    """ulp of |x| in the output type (x float64)."""
-    a = x.abs().clamp_min(2.0 ** -14 if dtype == F16 else 2.0 ** -126)         # subnormals: the ulp of the smallest normal
-    e = torch.floor(torch.log2(a))
-    return torch.exp2(e - (10 if dtype == F16 else 23))
-
-
-def _flip_slack(xd, X, delta, Wabs, dtype):
-    """slack on y = X W^T for rows X = round(xd) the kernel computed with an fp32 error up to `delta` per element before
-    rounding to the element type: an element within delta of a rounding boundary may round the other way (a whole ulp),
-    every other one rounds identically; fp32 rows carry delta itself"""
-    if dtype == F16:
-        u = _ulp(xd, F16)
-        near = ((xd - X).abs() - u / 2).abs() <= delta
-        return (near * u + delta) @ Wabs.T
-    return delta @ Wabs.T
-
-
-def _merge_ref(o, m, l):
-    """float64 merge of normalised partials o [S][..][64] with (m, l) [S][..]; returns (merged, merge error budget).
-    The kernels weight split s by exp(m_s - M) in fp32: the argument's rounding is ~|m_s - M| 2^-24 relative"""
-    md, ld, od = m.double(), l.double(), o.double()
-    M = md.max(0).values
-    w = torch.where(torch.isinf(md), torch.zeros_like(md), torch.exp(md - M)) * ld
-    w = w / w.sum(0)
-    x = (w.unsqueeze(-1) * od).sum(0)
-    arg = torch.where(torch.isinf(md), torch.zeros_like(md), (md - M).abs())
-    err = 2.0 ** -21 * (w.unsqueeze(-1) * (1.0 + arg.unsqueeze(-1)) * od.abs()).sum(0)
-    return x, err
-
-
-def _r(x, dtype):
-    return x.to(_tdt(dtype)).double()
 
 
 def _record(form, ratio):
@@ -191,14 +112,7 @@ def _gemv_case(dtype, R, N, K, pro=PLAIN, epi=STORE, bias=True, ln_folded=True, 
         else:
             lw, lb = 1.0 + 0.2 * torch.randn(K, generator=g), 0.1 * torch.randn(K, generator=g)
         lnw, lnb = lw.float().to(dev), lb.float().to(dev)
-        xd = xv.double().to(dev)
-        mu = xd.mean(1, keepdim=True)
-        var = ((xd - mu) ** 2).mean(1, keepdim=True)
-        xn = (xd - mu) / torch.sqrt(var + 1e-5) * lnw.double() + lnb.double()
-        X = _r(xn, dtype)
-        # the kernel's fp32 LayerNorm: one-pass mean of K values then a two-pass variance; its error on x^ grows with
-        # |mean| / std (the mean's rounding shifts every centred value)
-        delta = 2.0 ** -19 * (mu.abs() / torch.sqrt(var + 1e-5) + 1.0) * (xn.abs() + lnb.double().abs() + 1.0)
+        xn, X, delta, _, _ = ln_rows_ref(xv.double().to(dev), lnw, lnb, dtype)    # parity_ref: the kernel's fp32 LayerNorm error
         ln_slack = _flip_slack(xn, X, delta, Wd.abs(), dtype)
     else:
         H = K // 64
@@ -545,60 +459,10 @@ def _attn_case(dtype, H, R, Tk, splits, kv_group=1, vt=False, vt_short=False, kv
     # ---- float64 reference with the kernel's split boundaries and fp16 / fp32 partials
     gran = _granule(form, dtype)
     qs = _r(q.double() * 0.125, dtype)
-    ref = torch.zeros(R, D, dtype=torch.float64)
-    pv = torch.zeros(R, D, dtype=torch.float64)
-    pert = torch.zeros(R, D, dtype=torch.float64)
-    pe = torch.zeros(R, D, dtype=torch.float64)
-    pfl = torch.zeros(R, D, dtype=torch.float64)
-    for r in range(R):
-        T = lens[r]
-        b = r // kv_group
-        chunk = -(-T // splits)
-        chunk = -(-chunk // gran) * gran
-        for h in range(H):
-            kh = kk[b, :T, h * hs:h * hs + 64].double()
-            vh = vv[b, :T, h * hs:h * hs + 64].double()
-            s = kh @ qs[r, h * 64:(h + 1) * 64]
-            for drop_last in ((False, True) if T >= 2 else (False,)):
-                ms, ls, os_, fl = [], [], [], []
-                for sp in range(splits):
-                    k0, k1 = sp * chunk, min(T, (sp + 1) * chunk)
-                    if k1 <= k0:
-                        continue
-                    keep = torch.ones(k1 - k0, dtype=torch.bool)
-                    if drop_last:       # the last key (peaked scores: the peak key, the only one that matters there)
-                        j = int(s.argmax()) if peak else T - 1
-                        if k0 <= j < k1:
-                            keep[j - k0] = False
-                    if not keep.any():
-                        continue
-                    ss = s[k0:k1][keep]
-                    m = ss.max()
-                    p = torch.exp(ss - m)
-                    o = (p @ vh[k0:k1][keep]) / p.sum()
-                    ms.append(m); ls.append(p.sum()); os_.append(_r(o, dtype) if splits > 1 else o)
-                    # a partial within the kernel's fp32 error of a rounding boundary may round the other way
-                    de = (p * (1.0 + (ss - m).abs())) @ vh[k0:k1][keep].abs() / p.sum() * 2.0 ** -20
-                    u = _ulp(o, dtype)
-                    fl.append((((o - os_[-1]).abs() - u / 2).abs() <= de) * u if splits > 1 else torch.zeros_like(o))
-                M = max(ms)
-                w = torch.stack([torch.exp(m - M) * l for m, l in zip(ms, ls)])
-                o = (w.unsqueeze(1) * torch.stack(os_)).sum(0) / w.sum()
-                if not drop_last:
-                    pfl[r, h * 64:(h + 1) * 64] = (w.unsqueeze(1) * torch.stack(fl)).sum(0) / w.sum()
-                if drop_last:
-                    pert[r, h * 64:(h + 1) * 64] = o
-                else:
-                    ref[r, h * 64:(h + 1) * 64] = o
-                    p = torch.exp(s - s.max())
-                    # fp32 scores: exp(s - m) carries ~|s - m| 2^-24 relative error from the argument
-                    pv[r, h * 64:(h + 1) * 64] = (p @ vh.abs()) / p.sum()
-                    pe[r, h * 64:(h + 1) * 64] = (p * (1.0 + (s - s.max()).abs())) @ vh.abs() / p.sum()
-    ref, pv, pert, pe = ref.to(dev), pv.to(dev), pert.to(dev), pe.to(dev)
+    a = attn_ref(qs, lambda r, h: (kk[r // kv_group, :, h * hs:h * hs + 64].double(), vv[r // kv_group, :, h * hs:h * hs + 64].double()),
+                 lens, splits, gran, dtype, H, peak=bool(peak))
     c = C_ATT_MFMA if ("diag" in form or "mfma" in form) else C_ATT_VALU
-    bound = _ulp(ref, dtype) + c * pv + 2.0 ** -21 * pe
-    if splits > 1:                                                 # the split merge (merge_partials or in-launch)
-        bound = bound + 2.0 ** -21 * pe + pfl.to(dev)
+    ref, pert, bound = a["ref"].to(dev), a["pert"].to(dev), attn_bound(a, splits, c, dtype).to(dev)
     _check(form + ("/merge" if merge else ""), got, ref, bound, f"H={H} R={R} Tk={Tk} S={splits} G={kv_group}")
     if min(lens) >= 2:
         _sensitive(ref, pert, bound, "the last key dropped")

@@ -172,6 +172,8 @@ struct XAttnArgs {
   const void* W; const float* bias;               // fp16 [D][D], fp32 [D]
   int D, H, R;
   // cross K/V of row r (one audio per row): key j of head h at k + r*k_bs + j*k_ld + h*64
+  // Only keys [0, Tk) of a row are read (slots past a split's end, and every slot of an empty trailing split, re-read a key
+  // below Tk), Tk >= 1; nothing of k / v is written.
   const void* k; int64_t k_ld; int64_t k_bs;
   const void* v; int64_t v_ld; int64_t v_bs;
   int Tk, splits;
@@ -197,6 +199,10 @@ struct SAttnArgs {
   const void* W; const float* bias;               // fp16 [3D][D] = [query; key; value], fp32 [3D] (LayerNorm folded in)
   int D, H, R;
   void* kcache; void* vcache; int64_t cache_bs;   // this layer's self K / V [R][n_ctx][D]; row r appends at *d_pos - lag[r]
+  // With Tk = *d_pos - lag[r] + 1 >= 1: positions [0, Tk - 1) of row r are read and must hold the cached keys; position Tk - 1 is
+  // the only one written (D elements of K and of V) and its old bytes never reach a result, even at Tk == 1 where the tile
+  // loads them; positions >= Tk are neither read nor written.  launch_sattn8 refuses what sattn_supported does (cache_bs / D
+  // stands in for n_ctx) with hipErrorNotSupported.
   const int* d_pos; const int* lag;               // lag may be null
   void* q_out;                                    // optional: the unscaled q rows [R][D] (what the two-launch form leaves)
   void* out; int64_t o_ld;                        // attention output [R][D] (when x_out is null)

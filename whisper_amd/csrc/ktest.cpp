@@ -172,6 +172,40 @@ int wht_phrase_root_table(const int* child_begin, const int* child_token, const 
   return launch_phrase_root_table(child_begin, child_token, child_node, n_edges, V, root, (hipStream_t)stream);
 }
 
+// the fused attention launches of one decode step (xattn.hip): LayerNorm + projection + attention in one launch.  `mode` is
+// passed through (bit 0: scalar-path polls); att_in / x_out and the other optional-stage fields stay null, except that
+// `out_w` (cross) and `x_out` (self) are handed on as given so that a test can reach the launchers' refusal of the stages
+// the shipped build does not contain.
+int wht_xattn_supported(int D, int H, int R, int kv_group, int Tk, int splits) {
+  return xattn_supported(D, H, R, kv_group, Tk, splits) ? 1 : 0;
+}
+int wht_sattn_supported(int D, int H, int R, int n_ctx) { return sattn_supported(D, H, R, n_ctx) ? 1 : 0; }
+int wht_fused_mode(int kind) { return fused_mode(kind); }
+int wht_xattn8(const float* xf, int64_t xf_ld, const void* W, const float* bias, int D, int H, int R, const void* k,
+               int64_t k_ld, int64_t k_bs, const void* v, int64_t v_ld, int64_t v_bs, int Tk, int splits, void* out,
+               int64_t o_ld, void* part_o, float* part_ml, unsigned long long* qg, const int* d_tick, int epoch, int layer,
+               int* err, int mode, const void* out_w, void* stream) {
+  XAttnArgs a;
+  memset(&a, 0, sizeof a);
+  a.xf = xf; a.xf_ld = xf_ld; a.W = W; a.bias = bias; a.D = D; a.H = H; a.R = R;
+  a.k = k; a.k_ld = k_ld; a.k_bs = k_bs; a.v = v; a.v_ld = v_ld; a.v_bs = v_bs; a.Tk = Tk; a.splits = splits;
+  a.out = out; a.o_ld = o_ld; a.part_o = part_o; a.part_ml = part_ml;
+  a.qg = qg; a.d_tick = d_tick; a.epoch = epoch; a.layer = layer; a.err = err; a.mode = mode; a.out_w = out_w;
+  return launch_xattn8(a, (hipStream_t)stream);
+}
+int wht_sattn8(const float* xf, int64_t xf_ld, const void* W, const float* bias, int D, int H, int R, void* kcache,
+               void* vcache, int64_t cache_bs, const int* d_pos, const int* lag, void* q_out, void* out, int64_t o_ld,
+               unsigned long long* qg, const int* d_tick, int epoch, int layer, int* err, int mode, float* x_out,
+               void* stream) {
+  SAttnArgs a;
+  memset(&a, 0, sizeof a);
+  a.xf = xf; a.xf_ld = xf_ld; a.W = W; a.bias = bias; a.D = D; a.H = H; a.R = R;
+  a.kcache = kcache; a.vcache = vcache; a.cache_bs = cache_bs; a.d_pos = d_pos; a.lag = lag; a.q_out = q_out;
+  a.out = out; a.o_ld = o_ld; a.qg = qg; a.d_tick = d_tick; a.epoch = epoch; a.layer = layer; a.err = err; a.mode = mode;
+  a.x_out = x_out;
+  return launch_sattn8(a, (hipStream_t)stream);
+}
+
 // one beam-search update (beam.hip): the three launches of launch_beam_step on caller-supplied buffers.  B, G, K and R
 // are independent so that the launcher's own refusals can be reached; lag, lcp / copy_from and suppress_mask may be NULL.
 // `scratch` (wht_beam_scratch_bytes(R, V) bytes) is carved with beam_scratch_carve; wht_beam_cand_offsets gives the byte

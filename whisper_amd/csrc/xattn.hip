@@ -501,10 +501,12 @@ __global__ __launch_bounds__(768, 6) void xattn8_kernel(whk::XAttnArgs a) {
     const half_t* kp = (const half_t*)a.k + (int64_t)r * a.k_bs + h * 64 + cu * 8;
     const half_t* vp = (const half_t*)a.v + (int64_t)r * a.v_bs + h * 64 + cu * 8;
 #endif
-    const int klast = nkeys > 0 ? nkeys - 1 : 0;
+    // slots past the split's last key re-read that key; an EMPTY split (k0 >= Tk: the chunk is rounded up to 64 keys, so
+    // trailing splits can start past the row) re-reads key Tk - 1 — nothing at or beyond key Tk is ever touched
+    const int klast = k1 - 1;
     const uint32_t ldk = (uint32_t)a.k_ld, ldv = (uint32_t)a.v_ld;
-    const uint32_t ok0 = (uint32_t)(k0 + kk0) * ldk, okl = (uint32_t)(k0 + klast) * ldk;
-    const uint32_t ov0 = (uint32_t)(k0 + kk0) * ldv, ovl = (uint32_t)(k0 + klast) * ldv;
+    const uint32_t ok0 = (uint32_t)(k0 + kk0) * ldk, okl = (uint32_t)klast * ldk;
+    const uint32_t ov0 = (uint32_t)(k0 + kk0) * ldv, ovl = (uint32_t)klast * ldv;
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       uint32_t o = ok0 + (uint32_t)(i * KPR) * ldk; if (o > okl) o = okl;
@@ -851,8 +853,11 @@ __global__ __launch_bounds__(768, 6) void sattn8_kernel(whk::SAttnArgs a) {
       const float p = (sc[i] == WH_NEG_INF) ? 0.f : __expf(sc[i] - mx);
       sum += p;
       const half8v vv = (kk0 + i * KPR == Tk - 1) ? vnew : vu[i];
+      // a masked slot contributes a SELECTED 0, not 0 * v: at Tk == 1 its tile slot holds cache position 0, which this very
+      // launch is appending to — whatever bytes the load saw (the old ones may be NaN / Inf) must not reach the sum
+      const bool live = sc[i] != WH_NEG_INF;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] = __builtin_fmaf(p, (float)vv[e], acc[e]);
+      for (int e = 0; e < 8; ++e) acc[e] = __builtin_fmaf(p, live ? (float)vv[e] : 0.f, acc[e]);
     }
   }
   sum = across_groups8_sum(sum);
@@ -914,13 +919,18 @@ bool sattn_supported(int D, int H, int R, int n_ctx) {
 }
 
 hipError_t launch_sattn8(const SAttnArgs& a, hipStream_t stream) {
+  // the shapes of sattn_supported, re-checked like launch_xattn8 does; cache_bs / D stands in for n_ctx
+  if (a.D < 64 || !sattn_supported(a.D, a.H, a.R, (int)((a.cache_bs + a.D - 1) / a.D))) return hipErrorNotSupported;
+#ifndef WH_DEV
+  if (a.x_out) return hipErrorNotSupported;            // the third stage is compiled into development builds only
+#endif
   if ((int64_t)3 * a.D * a.D >= (1ll << 30) || (int64_t)a.D * 448 > 0x7fffffff) return hipErrorInvalidValue;
   hipLaunchKernelGGL(sattn8_kernel, dim3(3 * a.D / 8), dim3(768), 0, stream, a);
   return hipGetLastError();
 }
 
 hipError_t launch_xattn8(const XAttnArgs& a, hipStream_t stream) {
-  if (!xattn_supported(a.D, a.H, a.R, 1, a.Tk, a.splits)) return hipErrorNotSupported;
+  if (a.Tk < 1 || !xattn_supported(a.D, a.H, a.R, 1, a.Tk, a.splits)) return hipErrorNotSupported;
   if ((int64_t)a.k_ld * 2048 > 0x7fffffff || (int64_t)a.v_ld * 2048 > 0x7fffffff) return hipErrorInvalidValue;
   if ((int64_t)a.D * a.D >= (1ll << 30)) return hipErrorInvalidValue;          // 32-bit lane offsets into W
   const int chunk = (a.Tk + a.splits - 1) / a.splits;
