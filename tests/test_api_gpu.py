@@ -764,3 +764,56 @@ def test_transcribe_batch_in_flight_equals_one_lane(setup):
         gw = [[x["start"], x["end"]] for s in g["segments"] for x in s["words"]]
         ww = [[x["start"], x["end"]] for s in w["segments"] for x in s["words"]]
         assert gw == ww
+
+
+@pytest.fixture(scope="module")
+def wide16(gpu_device):
+    dims = dims_for("wide-v3")
+    sd = synthetic_state_dict(dims, seed=5, device=gpu_device)
+    return dims, hip.HipModel(dims, hip.WH_F16, hip.pack_weights(sd, dims, hip.WH_F16, gpu_device))
+
+
+@pytest.mark.parametrize("B,G", [(3, 1), (12, 1), (20, 1), (2, 5)])
+def test_bench_kernel_times_the_step_and_leaves_the_task_alone(wide16, gpu_device, B, G):
+    """wh_task_bench_kernel (HipTask.bench_kernel), every kind 0 - 7, on the step forms of 3 rows (fused cross attention), 12 rows
+    (in-launch merge), 20 rows (merge launch) and 2 x 5 beam rows (grouped cross attention over the transposed V): a positive
+    time, the documented algorithmic bytes per launch (api.cpp, bench_issue) recomputed here from the dims — integers below 2^53,
+    so equality is exact — the position where it was, no hand-off time-out, and the task's state untouched: the next step gives
+    bit for bit the logits of a twin task that was never measured."""
+    dims, model = wide16
+    R, T0, es = B * G, 4, 2
+    D, V, Ta, Ln = dims.n_text_state, dims.n_vocab, dims.n_audio_ctx, dims.n_text_layer
+    g = torch.Generator(device=gpu_device).manual_seed(21)
+    feats = torch.randn(B, Ta, D, generator=g, device=gpu_device).half()
+    toks = torch.randint(0, V, (R, T0 + 2), generator=g, device=gpu_device)
+    tasks = [hip.HipTask(model, B, G, 8) for _ in range(2)]
+    try:
+        for t in tasks:
+            t.set_audio(feats)
+            t.prefill(toks[:, :T0].contiguous(), sel=[T0 - 1])
+            t.step(toks[:, T0])
+        t = tasks[0]
+        pos = t.position
+        assert pos == T0 + 1
+        fx, fs = t.fused_cross_attention, t.fused_self_attention
+        assert fx == (R <= 8 and G == 1) and not fs
+        want = {
+            0: es * (Ln * 14 * D * D + V * D) + B * Ln * 2 * Ta * D * es + R * (pos + 1) * Ln * 2 * D * es + R * V * 4,
+            1: B * 2 * Ta * D * es + (D * D * es if fx else 0),
+            2: R * pos * 2 * D * es + (3 * D * D * es if fs else 0),
+            3: 3 * D * D * es, 4: 4 * D * D * es, 5: 4 * D * D * es,
+            6: V * D * es + R * V * 4,
+            7: D * D * es,
+        }
+        for kind in range(8):
+            ms, nbytes = t.bench_kernel(kind, 4)
+            assert ms > 0, kind
+            assert nbytes == float(want[kind]), (kind, nbytes, want[kind])
+            assert t.position == pos, kind
+        assert t.handoff_timeouts() == 0
+        a, b = (x.step(toks[:, T0 + 1]) for x in tasks)
+        assert torch.isfinite(a).all()
+        assert torch.equal(a, b), (a - b).abs().max().item()
+    finally:
+        for t in tasks:
+            t.destroy()

@@ -495,12 +495,18 @@ extern "C" int wh_task_create(const wh_model* m, int n_audio, int n_group, int m
   return WH_OK;
 }
 
+// both captured forms of the decode step; the next steps run eagerly and are captured again
+static void drop_step_graphs(wh_task* t) {
+  for (int i = 0; i < 2; ++i) {
+    if (t->graph_exec[i]) { (void)hipGraphExecDestroy(t->graph_exec[i]); t->graph_exec[i] = nullptr; }
+    if (t->graph[i]) { (void)hipGraphDestroy(t->graph[i]); t->graph[i] = nullptr; }
+    t->steps_eager[i] = 0;
+  }
+}
+
 extern "C" void wh_task_destroy(wh_task* t) {
   if (!t) return;
-  for (int i = 0; i < 2; ++i) {
-    if (t->graph_exec[i]) (void)hipGraphExecDestroy(t->graph_exec[i]);
-    if (t->graph[i]) (void)hipGraphDestroy(t->graph[i]);
-  }
+  drop_step_graphs(t);
   free(t->h_lag);
   if (t->h_poll) (void)hipHostFree(t->h_poll);
   if (t->h_sel) (void)hipHostFree(t->h_sel);
@@ -529,11 +535,6 @@ extern "C" int wh_task_info(wh_task* t, int what, void* stream) {
   return -1;
 }
 
-static int task_reset_impl(wh_task* t, void* stream_);
-extern "C" int wh_task_reset(wh_task* t, void* stream_) {
-  TASK_ENTER(t);
-  return task_reset_impl(t, stream_);
-}
 static int task_reset_impl(wh_task* t, void* stream_) {
   if (!t) return WH_ERR_ARG;
   hipStream_t s = (hipStream_t)stream_;
@@ -559,6 +560,10 @@ static int task_reset_impl(wh_task* t, void* stream_) {
   t->rep_on = false; t->rep = RepArgs{0, 1.0f};
   t->needs_reset = false;
   return WH_OK;
+}
+extern "C" int wh_task_reset(wh_task* t, void* stream_) {
+  TASK_ENTER(t);
+  return task_reset_impl(t, stream_);
 }
 
 // Ragged prompts: row r's token sequence is the longest row's shifted left by lag[r] (a shorter leading prompt).
@@ -615,6 +620,29 @@ extern "C" int wh_task_set_repetition(wh_task* t, int no_repeat_ngram_size, floa
   return WH_OK;
 }
 
+// ---- where layer l's caches live -------------------------------------------------------------------
+static inline void* self_k_layer(const wh_task* t, int l) {
+  const wh_dims& d = t->m->d;
+  return (char*)t->self_k + (size_t)l * t->R * d.n_text_ctx * d.n_text_state * t->m->esize;
+}
+static inline void* self_v_layer(const wh_task* t, int l) {
+  const wh_dims& d = t->m->d;
+  return (char*)t->self_v + (size_t)l * t->R * d.n_text_ctx * d.n_text_state * t->m->esize;
+}
+// cross K/V: key j of audio b is the row [K | V] at (b * Ta + j) * cross_ld; strides in elements
+static inline int64_t cross_ld(const wh_task* t) { return 2 * (int64_t)t->m->d.n_text_state; }
+static inline int64_t cross_bs(const wh_task* t) { return (int64_t)t->m->d.n_audio_ctx * cross_ld(t); }
+static inline void* cross_layer(const wh_task* t, int l) {
+  return (char*)t->cross_kv + (size_t)l * t->B * cross_bs(t) * t->m->esize;
+}
+static inline void* cross_v_layer(const wh_task* t, int l) {
+  return (char*)cross_layer(t, l) + (size_t)t->m->d.n_text_state * t->m->esize;
+}
+static inline int64_t cross_vt_bs(const wh_task* t) { return (int64_t)t->m->d.n_text_state * t->vt_ld; }
+static inline void* cross_vt_layer(const wh_task* t, int l) {    // only where t->cross_vt is set
+  return (char*)t->cross_vt + (size_t)l * t->B * cross_vt_bs(t) * t->m->esize;
+}
+
 extern "C" int wh_task_set_audio(wh_task* t, const void* features, void* stream_) {
   TASK_ENTER(t);
   if (!t || !features) return WH_ERR_ARG;
@@ -626,8 +654,7 @@ extern "C" int wh_task_set_audio(wh_task* t, const void* features, void* stream_
   const size_t es = m->esize;
   for (int l = 0; l < d.n_text_layer; ++l) {
     const wh_layer_weights& L = m->dec[l];
-    void* C = (char*)t->cross_kv + (size_t)l * M * 2 * D * es;
-    HIPCHK(gemm(m, features, D, L.ckv_w, D, C, 2 * D, M, 2 * D, L.ckv_b, 0, nullptr, 0, false, s));
+    HIPCHK(gemm(m, features, D, L.ckv_w, D, cross_layer(t, l), cross_ld(t), M, 2 * D, L.ckv_b, 0, nullptr, 0, false, s));
   }
   if (t->cross_vt) {
     // V^T = W_v . X^T per audio (bias along rows), as in the encoder; the pad columns [Ta, vt_ld) only have to be finite:
@@ -638,7 +665,7 @@ extern "C" int wh_task_set_audio(wh_task* t, const void* features, void* stream_
       GemmArgs g; memset(&g, 0, sizeof(g));
       g.A = (const char*)L.ckv_w + (size_t)D * D * es; g.lda = D; g.a_bs = 0;
       g.W = features; g.ldw = D; g.w_bs = (int64_t)Ta * D;
-      g.C = (char*)t->cross_vt + (size_t)l * t->B * D * t->vt_ld * es; g.ldc = t->vt_ld; g.c_bs = (int64_t)D * t->vt_ld;
+      g.C = cross_vt_layer(t, l); g.ldc = t->vt_ld; g.c_bs = cross_vt_bs(t);
       g.bias = L.ckv_b + D; g.bias_on_m = 1;
       g.M = D; g.N = Ta; g.K = D;
       HIPCHK(launch_gemm(g, m->dtype, 0, t->B, s));
@@ -648,39 +675,116 @@ extern "C" int wh_task_set_audio(wh_task* t, const void* features, void* stream_
   return WH_OK;
 }
 
-static inline void* self_k_layer(const wh_task* t, int l) {
-  const wh_dims& d = t->m->d;
-  return (char*)t->self_k + (size_t)l * t->R * d.n_text_ctx * d.n_text_state * t->m->esize;
-}
-static inline void* self_v_layer(const wh_task* t, int l) {
-  const wh_dims& d = t->m->d;
-  return (char*)t->self_v + (size_t)l * t->R * d.n_text_ctx * d.n_text_state * t->m->esize;
-}
-static inline void* cross_layer(const wh_task* t, int l) {
-  const wh_dims& d = t->m->d;
-  return (char*)t->cross_kv + (size_t)l * t->B * d.n_audio_ctx * 2 * d.n_text_state * t->m->esize;
+// ---- the launches of one decoder layer, described once --------------------------------------------------
+// The decode step (step_launch), the few-row prefill (prefill_impl) and the per-kernel measurement hook (bench_issue) build
+// their argument structs here: a builder fills the prologue and the shape, the caller sets the epilogue and launches.
+
+// How the launches of one decode step hand their activations on (decided once per task shape).
+//  * Fragment-order hand-offs (kernels.h): an activation that goes from one launch straight into a PRO_PLAIN projection is written
+//    by its producer in the order that projection's lanes read it — only where BOTH ends are launches that know the order (fp16,
+//    <= 24 rows: gemv8_kernel).  A/B: WH_NO_FRAGMENT_ORDER=1.
+//  * Up to 16 rows the per-row cross attention (no beam groups) with 2 - 4 key splits merges its partials in the launch
+//    (attention.hip: the last workgroup of a (row, head) to finish), so cross_attn.out is a plain projection without a merge
+//    prologue: 9 / 12 / 16 rows 1753 / 1816 / 1999 -> 1701 / 1770 / 1973 us per step.  At 17 - 24 rows the tickets of 1440
+//    workgroups cost more than the merge launch they replace (24 rows 2448 -> 2471): that launch stays.  A/B: WH_NO_TAIL_MERGE=1.
+struct StepPlan { bool frag_att, frag_self, frag_mlp, tail_merge; };
+static StepPlan step_plan(const wh_task* t) {
+  const wh_model* m = t->m;
+  const int D = m->d.n_text_state, R = t->R;
+  StepPlan p;
+  const bool frag_on = m->dtype == WH_F16 && !WH_DEV_FLAG("WH_NO_FRAGMENT_ORDER");
+  p.frag_att = frag_on && gemv8_will_run(R, D, D, PRO_PLAIN);                              // attention output -> D x D projection
+  p.frag_self = p.frag_att && !t->fused_sattn && !t->fused_xout && t->self_splits <= 1;
+  p.frag_mlp = frag_on && (m->w.flags & WH_WEIGHTS_DEC_LN_FOLDED) && gemv8_will_run(R, 4 * D, D, PRO_LN) &&
+               gemv8_will_run(R, D, 4 * D, PRO_PLAIN);                                    // FC1 -> FC2
+  p.tail_merge = m->dtype == WH_F16 && !t->fused_xattn && t->G == 1 && R <= 16 && t->cross_splits >= 2 &&
+                 t->cross_splits <= 4 && !WH_DEV_FLAG("WH_NO_TAIL_MERGE");
+  return p;
 }
 
-// ---- skinny projections of the prefill -------------------------------------------------------------
-// The usual prefill is a handful of rows (batch x 3-4 initial tokens): a 128x128 MFMA tile would be > 80 % padding
-// and its launch fills 10-40 workgroups, so up to SKINNY_ROWS rows go through the decode-step projection kernels
-// (LayerNorm / residual fused, weights streamed once); long prompts keep the GEMM path.
-
-static hipError_t proj_ln(const wh_model* m, const float* x, int rows, const float* ln_w, const float* ln_b, const void* W,
-                          const float* bias, int N, int K, void* y, int64_t y_ld, bool gelu, hipStream_t s) {
+// LayerNorm(x) -> W (QKV, cross query, FC1; the tied logits projection through logits_proj)
+static GemvArgs ln_proj(const wh_model* m, const float* x, int rows, const float* ln_w, const float* ln_b, const void* W,
+                        const float* bias, int N, int K) {
   GemvArgs g; memset(&g, 0, sizeof(g));
   g.pro = PRO_LN; g.xf = x; g.xf_ld = K; g.ln_w = ln_w; g.ln_b = ln_b; g.ln_folded = (m->w.flags & WH_WEIGHTS_DEC_LN_FOLDED) ? 1 : 0;
   g.W = W; g.bias = bias; g.N = N; g.K = K; g.R = rows;
-  g.epi = gelu ? EPI_GELU : EPI_STORE; g.y = y; g.y_ld = y_ld;
+  return g;
+}
+// the decoder's last LayerNorm -> token embedding (never folded: the matrix is the embedding table too), fp32 logits
+static GemvArgs logits_proj(const wh_model* m, const float* x, int rows, float* logits, int64_t logits_ld) {
+  const int D = m->d.n_text_state;
+  GemvArgs g = ln_proj(m, x, rows, m->w.dec_ln_w, m->w.dec_ln_b, m->w.tok_emb, nullptr, m->d.n_vocab, D);
+  g.ln_folded = 0;
+  g.epi = EPI_F32; g.y = logits; g.y_ld = logits_ld;
+  return g;
+}
+// attention output / FC1 output -> W (self out, cross out, FC2): the rows of x as they are (x_frag: in fragment order), or
+// with splits > 1 the merge of the decode attention's key-split partials as the prologue
+static GemvArgs plain_proj(const wh_task* t, const void* x, int64_t x_ld, bool x_frag, int splits, int rows, const void* W,
+                           const float* bias, int N, int K) {
+  GemvArgs g; memset(&g, 0, sizeof(g));
+  if (splits > 1) { g.pro = PRO_COMBINE; g.part_o = t->part_o; g.part_ml = t->part_ml; g.splits = splits; g.H = t->m->d.n_text_head; }
+  else { g.pro = PRO_PLAIN; g.x = x; g.x_ld = x_ld; g.x_frag = x_frag; }
+  g.W = W; g.bias = bias; g.N = N; g.K = K; g.R = rows;
+  return g;
+}
+// epilogues: y = act(...) in the element type / resid += ...
+static hipError_t gemv_store(const wh_model* m, GemvArgs g, int epi, void* y, int64_t y_ld, bool y_frag, hipStream_t s) {
+  g.epi = epi; g.y = y; g.y_ld = y_ld; g.y_frag = y_frag;
   return launch_gemv(g, m->dtype, s);
 }
-static hipError_t proj_resid(const wh_model* m, const void* x, int64_t x_ld, int rows, const void* W, const float* bias,
-                             int N, int K, float* resid, hipStream_t s) {
-  GemvArgs g; memset(&g, 0, sizeof(g));
-  g.pro = PRO_PLAIN; g.x = x; g.x_ld = x_ld;
-  g.W = W; g.bias = bias; g.N = N; g.K = K; g.R = rows;
-  g.epi = EPI_RESID; g.resid = resid; g.resid_ld = N;
+static hipError_t gemv_resid(const wh_model* m, GemvArgs g, float* resid, hipStream_t s) {
+  g.epi = EPI_RESID; g.resid = resid; g.resid_ld = g.N;
   return launch_gemv(g, m->dtype, s);
+}
+
+// self attention of the step's one new query per row over the cached keys: *d_pos + len_plus of them
+static DecAttnArgs self_attn_args(const wh_task* t, int l, const StepPlan& plan, int len_plus) {
+  const wh_dims& d = t->m->d;
+  const int D = d.n_text_state;
+  DecAttnArgs a; memset(&a, 0, sizeof(a));
+  a.q = t->qbuf; a.q_ld = D;
+  a.k = self_k_layer(t, l); a.k_ld = D; a.k_bs = (int64_t)d.n_text_ctx * D;
+  a.v = self_v_layer(t, l); a.v_ld = D; a.v_bs = a.k_bs;
+  a.H = d.n_text_head; a.R = t->R; a.kv_group = 1; a.d_len = t->d_pos; a.len_plus = len_plus; a.splits = t->self_splits;
+  a.lag = t->d_lag;
+  a.out = t->att; a.o_ld = D; a.o_frag = plan.frag_self; a.part_o = t->part_o; a.part_ml = t->part_ml;
+  return a;
+}
+// cross attention of `rows` single-query rows, kv_group consecutive rows per audio, over layer l's cached audio K/V.
+// step: the decode step's form (the in-launch merge where the plan has it, the transposed V where the task keeps one);
+// null: the few-row prefill's
+static DecAttnArgs cross_attn_args(const wh_task* t, int l, const void* q, int rows, int kv_group, int splits,
+                                   const StepPlan* step) {
+  const wh_dims& d = t->m->d;
+  const int D = d.n_text_state;
+  DecAttnArgs a; memset(&a, 0, sizeof(a));
+  a.q = q; a.q_ld = D;
+  a.k = cross_layer(t, l); a.k_ld = cross_ld(t); a.k_bs = cross_bs(t);
+  a.v = cross_v_layer(t, l); a.v_ld = a.k_ld; a.v_bs = a.k_bs;
+  a.H = d.n_text_head; a.R = rows; a.kv_group = kv_group; a.Tk = d.n_audio_ctx; a.splits = splits;
+  a.out = t->att; a.o_ld = D; a.part_o = t->part_o; a.part_ml = t->part_ml;
+  if (step && step->tail_merge) { a.merge_cnt = t->merge_cnt; a.o_frag = step->frag_att; }
+  if (step && t->cross_vt) { a.vt = cross_vt_layer(t, l); a.vt_ld = t->vt_ld; a.vt_bs = cross_vt_bs(t); }
+  return a;
+}
+// resid += cross_attn.out of the decode step: where the attention launch left its partials decides the prologue
+static int launch_cross_out(const wh_task* t, const StepPlan& plan, const wh_layer_weights& L, float* resid, hipStream_t s) {
+  const wh_model* m = t->m;
+  const int D = m->d.n_text_state, R = t->R;
+  // 17+ rows (beam search): the projection runs as 16-row workgroups that would each merge their rows' partials
+  // again, so the merge is a launch of its own there (A/B: WH_NO_MERGE_KERNEL=1)
+  const bool merge_kernel = !WH_DEV_FLAG("WH_NO_MERGE_KERNEL");   // developer A/B switch
+  int splits = t->cross_splits;
+  bool frag = false;
+  if (plan.tail_merge) {            // merged inside the attention launch by the last workgroup of each (row, head)
+    splits = 1; frag = plan.frag_att;
+  } else if (splits > 1 && R > 16 && m->dtype == WH_F16 && merge_kernel) {   // the fp32 engine keeps one code path
+    HIPCHK(launch_merge_partials(t->part_o, t->part_ml, splits, R, m->d.n_text_head, t->att, D, m->dtype, s, plan.frag_att));
+    splits = 1; frag = plan.frag_att;
+  }
+  HIPCHK(gemv_resid(m, plain_proj(t, t->att, D, frag, splits, R, L.cout_w, L.cout_b, D, D), resid, s));
+  return WH_OK;
 }
 
 // ---- prefill: T0 tokens per row through the GEMM path ------------------------------------------
@@ -707,6 +811,22 @@ static size_t score_carve(size_t Ms, int V, void* base, int** target, void** par
   return align_up(c.off, 256);
 }
 
+// The prefill's selected row indices (and the scorer's row lengths) reach t->d_sel through pinned words the task owns, so
+// that the copy needs no host synchronisation behind it (the fused loops' begin calls must not wait for the device).
+// selection_words hands the words out once an earlier call's copy has executed — it has, unless calls follow each other
+// faster than the stream drains; selection_copy queues the copy of the first n of them and records the event behind it.
+static int selection_words(wh_task* t, int** out) {
+  if (!t->h_sel) HIPCHK(hipHostMalloc((void**)&t->h_sel, (size_t)t->R * t->Tmax * sizeof(int), hipHostMallocDefault));
+  if (!t->sel_event) HIPCHK(hipEventCreateWithFlags(&t->sel_event, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(t->sel_event));
+  *out = t->h_sel;
+  return WH_OK;
+}
+static hipError_t selection_copy(wh_task* t, int n, hipStream_t s) {
+  const hipError_t e = hipMemcpyAsync(t->d_sel, t->h_sel, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s);
+  return e != hipSuccess ? e : hipEventRecord(t->sel_event, s);
+}
+
 static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride, int T0, const int32_t* sel_pos,
                         int n_sel, float* logits_out, int64_t logits_row_ld, hipStream_t s, bool leaders = false,
                         const ScoreReq* sc = nullptr) {
@@ -726,6 +846,9 @@ static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride,
     for (int r = 0; r < R; ++r) if (t->h_lag[r * lag_step] >= T0) return WH_ERR_ARG;
   }
 
+  // The usual prefill is a handful of rows (batch x 3-4 initial tokens): a 128x128 MFMA tile would be > 80 % padding
+  // and its launch fills 10-40 workgroups, so up to SKINNY_ROWS rows go through the decode-step projection kernels
+  // (LayerNorm / residual fused, weights streamed once); long prompts keep the GEMM path.
   // scoring always takes the GEMM path: a row's numbers then do not depend on how many rows it was batched with
   const bool skinny = !sc && M <= SKINNY_ROWS && D <= 2048;
   // one row per audio (alignment tasks; beam search through its leader rows) and a transposed V: flash cross attention
@@ -737,7 +860,7 @@ static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride,
     const wh_layer_weights& L = m->dec[l];
     // self attention (causal over cached + new positions)
     if (skinny) {
-      HIPCHK(proj_ln(m, t->x, M, L.attn_ln_w, L.attn_ln_b, L.qkv_w, L.qkv_b, 3 * D, D, t->qkv, 3 * D, false, s));
+      HIPCHK(gemv_store(m, ln_proj(m, t->x, M, L.attn_ln_w, L.attn_ln_b, L.qkv_w, L.qkv_b, 3 * D, D), EPI_STORE, t->qkv, 3 * D, false, s));
     } else {
       HIPCHK(launch_layernorm(t->x, D, L.attn_ln_w, L.attn_ln_b, t->xn, D, M, D, m->dtype, s));
       HIPCHK(gemm(m, t->xn, D, L.qkv_w, D, t->qkv, 3 * D, M, 3 * D, L.qkv_b, 0, nullptr, 0, false, s));
@@ -753,8 +876,8 @@ static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride,
       HIPCHK(launch_attn_generic(a, R, m->dtype, s));
     }
     if (skinny) {
-      HIPCHK(proj_resid(m, t->att, D, M, L.out_w, L.out_b, D, D, t->x, s));
-      HIPCHK(proj_ln(m, t->x, M, L.cross_ln_w, L.cross_ln_b, L.cq_w, L.cq_b, D, D, t->qkv, D, false, s));
+      HIPCHK(gemv_resid(m, plain_proj(t, t->att, D, false, 1, M, L.out_w, L.out_b, D, D), t->x, s));
+      HIPCHK(gemv_store(m, ln_proj(m, t->x, M, L.cross_ln_w, L.cross_ln_b, L.cq_w, L.cq_b, D, D), EPI_STORE, t->qkv, D, false, s));
     } else {
       HIPCHK(gemm(m, t->att, D, L.out_w, D, t->x, D, M, D, L.out_b, 0, t->x, D, true, s));
       // cross attention over the cached audio K/V
@@ -772,37 +895,26 @@ static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride,
       // rows (r, t) are M independent single-query rows of the decode cross attention; the T0 * G rows of one
       // audio share its K/V (one workgroup per (split, head, audio) when T0 * G <= 8)
       const int ps = pick_splits(M, H, Ta, m->dtype);
-      DecAttnArgs a; memset(&a, 0, sizeof(a));
-      a.q = t->qkv; a.q_ld = D;
-      a.k = cross_layer(t, l); a.k_ld = 2 * D; a.k_bs = (int64_t)Ta * 2 * D;
-      a.v = (char*)cross_layer(t, l) + (size_t)D * es; a.v_ld = 2 * D; a.v_bs = a.k_bs;
-      a.H = H; a.R = M; a.kv_group = T0 * Gp; a.Tk = Ta; a.splits = ps;
-      a.out = t->att; a.o_ld = D; a.part_o = t->part_o; a.part_ml = t->part_ml;
-      HIPCHK(launch_attn_decode(a, m->dtype, s));
-      GemvArgs g; memset(&g, 0, sizeof(g));
-      if (ps > 1) { g.pro = PRO_COMBINE; g.part_o = t->part_o; g.part_ml = t->part_ml; g.splits = ps; g.H = H; }
-      else { g.pro = PRO_PLAIN; g.x = t->att; g.x_ld = D; }
-      g.W = L.cout_w; g.bias = L.cout_b; g.N = D; g.K = D; g.R = M;
-      g.epi = EPI_RESID; g.resid = t->x; g.resid_ld = D;
-      HIPCHK(launch_gemv(g, m->dtype, s));
+      HIPCHK(launch_attn_decode(cross_attn_args(t, l, t->qkv, M, T0 * Gp, ps, nullptr), m->dtype, s));
+      HIPCHK(gemv_resid(m, plain_proj(t, t->att, D, false, ps, M, L.cout_w, L.cout_b, D, D), t->x, s));
     } else if (flash_cross) {
       // T0 queries x 1500 keys per row on the encoder's flash-attention kernel (MFMA; unscaled q / k: it applies
       // d_head^-0.5 itself): the generic kernel took 1.4 ms per layer for 32 rows x 205 tokens (profiles/r03_kernel_stats_extras.csv)
-      HIPCHK(launch_attn_flash_f16(t->qkv, D, (int64_t)T0 * D, cross_layer(t, l), 2 * D, (int64_t)Ta * 2 * D,
-                                   (char*)t->cross_vt + (size_t)l * t->B * D * t->vt_ld * es, t->vt_ld, (int64_t)D * t->vt_ld,
+      HIPCHK(launch_attn_flash_f16(t->qkv, D, (int64_t)T0 * D, cross_layer(t, l), cross_ld(t), cross_bs(t),
+                                   cross_vt_layer(t, l), t->vt_ld, cross_vt_bs(t),
                                    t->att, D, (int64_t)T0 * D, R, H, Ta, 0, s, T0));
     } else {
       AttnArgs a; memset(&a, 0, sizeof(a));
       a.q = t->qkv; a.q_ld = D; a.q_bs = (int64_t)T0 * D;
-      a.k = cross_layer(t, l); a.k_ld = 2 * D; a.k_bs = (int64_t)Ta * 2 * D;
-      a.v = (char*)cross_layer(t, l) + (size_t)D * es; a.v_ld = 2 * D; a.v_bs = a.k_bs;
+      a.k = cross_layer(t, l); a.k_ld = cross_ld(t); a.k_bs = cross_bs(t);
+      a.v = cross_v_layer(t, l); a.v_ld = a.k_ld; a.v_bs = a.k_bs;
       a.out = t->att; a.o_ld = D; a.o_bs = (int64_t)T0 * D;
       a.H = H; a.Tq = T0; a.Tk = Ta; a.causal = 0; a.kv_group = Gp;
       HIPCHK(launch_attn_generic(a, R, m->dtype, s));
     }
     if (skinny) {
-      HIPCHK(proj_ln(m, t->x, M, L.mlp_ln_w, L.mlp_ln_b, L.fc1_w, L.fc1_b, 4 * D, D, t->h, 4 * D, true, s));
-      HIPCHK(proj_resid(m, t->h, 4 * D, M, L.fc2_w, L.fc2_b, D, 4 * D, t->x, s));
+      HIPCHK(gemv_store(m, ln_proj(m, t->x, M, L.mlp_ln_w, L.mlp_ln_b, L.fc1_w, L.fc1_b, 4 * D, D), EPI_GELU, t->h, 4 * D, false, s));
+      HIPCHK(gemv_resid(m, plain_proj(t, t->h, 4 * D, false, 1, M, L.fc2_w, L.fc2_b, D, 4 * D), t->x, s));
     } else {
       HIPCHK(gemm(m, t->att, D, L.cout_w, D, t->x, D, M, D, L.cout_b, 0, t->x, D, true, s));
       // MLP
@@ -812,18 +924,16 @@ static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride,
     }
   }
   if (sc) {
-    // selected rows and valid lengths go through the task's pinned words in one copy (see below): [Ms rows][R lengths],
+    // selected rows and valid lengths go through the task's pinned words in one copy (selection_words): [Ms rows][R lengths],
     // Ms = R (T0 - 1 - first) <= R (Tmax - 1)
     const int n_out = T0 - 1 - sc->first, Ms = R * n_out;
-    if (!t->h_sel) HIPCHK(hipHostMalloc((void**)&t->h_sel, (size_t)t->R * t->Tmax * sizeof(int), hipHostMallocDefault));
-    if (!t->sel_event) HIPCHK(hipEventCreateWithFlags(&t->sel_event, hipEventDisableTiming));
-    else HIPCHK(hipEventSynchronize(t->sel_event));
-    int* sel = t->h_sel;
+    int* sel;
+    const int rc = selection_words(t, &sel);
+    if (rc != WH_OK) return rc;
     for (int r = 0; r < R; ++r)
       for (int i = 0; i < n_out; ++i) sel[(size_t)r * n_out + i] = r * T0 + sc->first + i;
     for (int r = 0; r < R; ++r) sel[(size_t)Ms + r] = sc->n_tok[r];
-    HIPCHK(hipMemcpyAsync(t->d_sel, sel, (size_t)(Ms + R) * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(t->sel_event, s));
+    HIPCHK(selection_copy(t, Ms + R, s));
     int* target; void* part; size_t part_bytes;
     score_carve((size_t)Ms, V, sc->scratch, &target, &part, &part_bytes);
     HIPCHK(launch_score_targets(tokens, token_stride, t->d_sel + Ms, R, n_out, sc->first, target, s));
@@ -832,13 +942,9 @@ static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride,
     HIPCHK(launch_score(t->xseln, D, m->w.tok_emb, D, target, Ms, D, V, sc->v_end, sc->logprob, sc->top_logprob,
                         sc->top_token, part, part_bytes, m->dtype, s));
   } else if (logits_out && n_sel > 0) {        // logits of the selected positions
-    // the row indices go through pinned memory the task owns, so that the copy needs no host synchronisation behind it (the
-    // fused loops' begin calls must not wait for the device); an earlier call's copy has to have executed before the words
-    // are rewritten — it has, unless calls follow each other faster than the stream drains
-    if (!t->h_sel) HIPCHK(hipHostMalloc((void**)&t->h_sel, (size_t)t->R * t->Tmax * sizeof(int), hipHostMallocDefault));
-    if (!t->sel_event) HIPCHK(hipEventCreateWithFlags(&t->sel_event, hipEventDisableTiming));
-    else HIPCHK(hipEventSynchronize(t->sel_event));
-    int* sel = t->h_sel;
+    int* sel;
+    const int rc = selection_words(t, &sel);
+    if (rc != WH_OK) return rc;
     for (int r = 0; r < R; ++r)
       for (int i = 0; i < n_sel; ++i) {
         const int p = (sel_pos ? sel_pos[i] : i) - (sel_pos ? t->h_lag[r * lag_step] : 0);   // selected positions shift with the row
@@ -846,15 +952,10 @@ static int prefill_impl(wh_task* t, const int64_t* tokens, int64_t token_stride,
         sel[(size_t)r * n_sel + i] = r * T0 + p;
       }
     const int Ms = R * n_sel;
-    HIPCHK(hipMemcpyAsync(t->d_sel, sel, (size_t)Ms * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(t->sel_event, s));
+    HIPCHK(selection_copy(t, Ms, s));
     HIPCHK(launch_gather_rows(t->x, t->d_sel, Ms, D, t->xsel, s));
     if (Ms <= SKINNY_LOGIT_ROWS && D <= 2048) {    // LayerNorm + tied logits projection as one streaming launch
-      GemvArgs g; memset(&g, 0, sizeof(g));
-      g.pro = PRO_LN; g.xf = t->xsel; g.xf_ld = D; g.ln_w = m->w.dec_ln_w; g.ln_b = m->w.dec_ln_b;
-      g.W = m->w.tok_emb; g.N = V; g.K = D; g.R = Ms;
-      g.epi = EPI_F32; g.y = logits_out; g.y_ld = logits_row_ld;
-      HIPCHK(launch_gemv(g, m->dtype, s));
+      HIPCHK(launch_gemv(logits_proj(m, t->xsel, Ms, logits_out, logits_row_ld), m->dtype, s));
     } else {
       HIPCHK(launch_layernorm(t->xsel, D, m->w.dec_ln_w, m->w.dec_ln_b, t->xseln, D, Ms, D, m->dtype, s));
       GemmArgs g; memset(&g, 0, sizeof(g));
@@ -898,18 +999,17 @@ extern "C" int wh_task_score(wh_task* t, const int64_t* tokens, int64_t token_st
   return prefill_impl(t, tokens, token_stride, T0, nullptr, 0, nullptr, 0, (hipStream_t)stream, false, &sc);
 }
 
-static inline void* cross_layer(const wh_task* t, int l);
 // arguments of the fused LN -> cross query -> cross attention launch of layer l (xattn.hip)
 static XAttnArgs xattn_args(const wh_task* t, int l, int epoch, float* x_in, bool with_out = false) {
   const wh_model* m = t->m;
   const wh_dims& d = m->d;
-  const int D = d.n_text_state, Ta = d.n_audio_ctx;
+  const int D = d.n_text_state;
   const wh_layer_weights& L = m->dec[l];
   XAttnArgs a; memset(&a, 0, sizeof(a));
   a.xf = x_in; a.xf_ld = D; a.W = L.cq_w; a.bias = L.cq_b; a.D = D; a.H = d.n_text_head; a.R = t->R;
-  a.k = cross_layer(t, l); a.k_ld = 2 * D; a.k_bs = (int64_t)Ta * 2 * D;
-  a.v = (char*)cross_layer(t, l) + (size_t)D * m->esize; a.v_ld = 2 * D; a.v_bs = a.k_bs;
-  a.Tk = Ta; a.splits = t->cross_splits;
+  a.k = cross_layer(t, l); a.k_ld = cross_ld(t); a.k_bs = cross_bs(t);
+  a.v = cross_v_layer(t, l); a.v_ld = a.k_ld; a.v_bs = a.k_bs;
+  a.Tk = d.n_audio_ctx; a.splits = t->cross_splits;
   a.out = t->att; a.o_ld = D; a.part_o = t->part_o; a.part_ml = t->part_ml;
   a.qg = t->xq_gran; a.d_tick = t->d_tick; a.epoch = epoch; a.layer = l; a.err = t->d_err; a.mode = fused_mode(0) | ((t->flags & WH_TASK_EXPIRE_HANDOFFS) ? 4 : 0);
   if (with_out) {      // phase 0: x_in += attn.out(t->att) + bias, in place, before the LayerNorm of this launch
@@ -918,8 +1018,6 @@ static XAttnArgs xattn_args(const wh_task* t, int l, int epoch, float* x_in, boo
   return a;
 }
 
-static inline void* self_k_layer(const wh_task* t, int l);
-static inline void* self_v_layer(const wh_task* t, int l);
 // arguments of the fused LN -> QKV -> cache append -> self attention launch of layer l (xattn.hip)
 // x_in: the residual stream the layer starts from; x_out (or null): where x_in + attn.out(attention) goes when the output
 // projection runs inside the same launch
@@ -939,36 +1037,11 @@ static SAttnArgs sattn_args(const wh_task* t, int l, int epoch, const float* x_i
 }
 
 // ---- one decode step (all kernels read the position from *d_pos: graph-replayable) ---------------
-// How the launches of one decode step hand their activations on (decided once per task shape; step_launch and the per-kernel
-// bench below read the same plan).
-//  * Fragment-order hand-offs (kernels.h): an activation that goes from one launch straight into a PRO_PLAIN projection is written
-//    by its producer in the order that projection's lanes read it — only where BOTH ends are launches that know the order (fp16,
-//    <= 24 rows: gemv8_kernel).  A/B: WH_NO_FRAGMENT_ORDER=1.
-//  * Up to 16 rows the per-row cross attention (no beam groups) with 2 - 4 key splits merges its partials in the launch
-//    (attention.hip: the last workgroup of a (row, head) to finish), so cross_attn.out is a plain projection without a merge
-//    prologue: 9 / 12 / 16 rows 1753 / 1816 / 1999 -> 1701 / 1770 / 1973 us per step.  At 17 - 24 rows the tickets of 1440
-//    workgroups cost more than the merge launch they replace (24 rows 2448 -> 2471): that launch stays.  A/B: WH_NO_TAIL_MERGE=1.
-struct StepPlan { bool frag_att, frag_self, frag_mlp, tail_merge; };
-static StepPlan step_plan(const wh_task* t) {
-  const wh_model* m = t->m;
-  const int D = m->d.n_text_state, R = t->R;
-  StepPlan p;
-  const bool frag_on = m->dtype == WH_F16 && !WH_DEV_FLAG("WH_NO_FRAGMENT_ORDER");
-  p.frag_att = frag_on && gemv8_will_run(R, D, D, PRO_PLAIN);                              // attention output -> D x D projection
-  p.frag_self = p.frag_att && !t->fused_sattn && !t->fused_xout && t->self_splits <= 1;
-  p.frag_mlp = frag_on && (m->w.flags & WH_WEIGHTS_DEC_LN_FOLDED) && gemv8_will_run(R, 4 * D, D, PRO_LN) &&
-               gemv8_will_run(R, D, 4 * D, PRO_PLAIN);                                    // FC1 -> FC2
-  p.tail_merge = m->dtype == WH_F16 && !t->fused_xattn && t->G == 1 && R <= 16 && t->cross_splits >= 2 &&
-                 t->cross_splits <= 4 && !WH_DEV_FLAG("WH_NO_TAIL_MERGE");
-  return p;
-}
-
 static int step_launch(wh_task* t, hipStream_t s, bool embedded = false) {
   const wh_model* m = t->m;
   const wh_dims& d = m->d;
-  const int D = d.n_text_state, H = d.n_text_head, C = d.n_text_ctx, Ta = d.n_audio_ctx, V = d.n_vocab;
+  const int D = d.n_text_state, C = d.n_text_ctx, V = d.n_vocab;
   const int R = t->R;
-  const size_t es = m->esize;
   if (!embedded)
     HIPCHK(launch_embed(t->step_tokens, 1, R, 1, m->w.tok_emb, m->w.dec_pos, t->d_pos, t->d_lag, D, V, t->x, m->dtype, s));
   // the residual stream of the step: starts in t->x (embedding / the sampler's x_next); a self-attention launch that also
@@ -976,110 +1049,44 @@ static int step_launch(wh_task* t, hipStream_t s, bool embedded = false) {
   float* xc = t->x;
   float* xo = t->x2;
   const StepPlan plan = step_plan(t);
-  const bool frag_att = plan.frag_att, frag_self = plan.frag_self, frag_mlp = plan.frag_mlp, tail_merge = plan.tail_merge;
   for (int l = 0; l < d.n_text_layer; ++l) {
     const wh_layer_weights& L = m->dec[l];
-    GemvArgs g;
     bool out_done = false;
     if (t->fused_sattn) {
       // LN -> QKV -> cache append -> self attention [-> attn.out + residual] as ONE launch (xattn.hip, sattn8_kernel)
       HIPCHK(launch_sattn8(sattn_args(t, l, 0, xc, t->fused_out ? xo : nullptr), s));
       if (t->fused_out) { float* tmp = xc; xc = xo; xo = tmp; out_done = true; }
     } else {
-    // LN -> QKV, K/V appended in place at *d_pos
-    memset(&g, 0, sizeof(g));
-    g.pro = PRO_LN; g.xf = xc; g.xf_ld = D; g.ln_w = L.attn_ln_w; g.ln_b = L.attn_ln_b; g.ln_folded = (m->w.flags & WH_WEIGHTS_DEC_LN_FOLDED) ? 1 : 0;
-    g.W = L.qkv_w; g.bias = L.qkv_b; g.N = 3 * D; g.K = D; g.R = R;
-    g.epi = EPI_QKV; g.y = t->qbuf; g.y_ld = D;
-    g.kcache = self_k_layer(t, l); g.vcache = self_v_layer(t, l); g.cache_bs = (int64_t)C * D; g.d_pos = t->d_pos; g.D = D;
-    g.lag = t->d_lag;
-    HIPCHK(launch_gemv(g, m->dtype, s));
-    {
-      DecAttnArgs a; memset(&a, 0, sizeof(a));
-      a.q = t->qbuf; a.q_ld = D;
-      a.k = self_k_layer(t, l); a.k_ld = D; a.k_bs = (int64_t)C * D;
-      a.v = self_v_layer(t, l); a.v_ld = D; a.v_bs = (int64_t)C * D;
-      a.H = H; a.R = R; a.kv_group = 1; a.d_len = t->d_pos; a.len_plus = 1; a.splits = t->self_splits;
-      a.lag = t->d_lag;
-      a.out = t->att; a.o_ld = D; a.o_frag = frag_self; a.part_o = t->part_o; a.part_ml = t->part_ml;
-      HIPCHK(launch_attn_decode(a, m->dtype, s));
-    }
+      // LN -> QKV, K/V appended in place at *d_pos
+      GemvArgs g = ln_proj(m, xc, R, L.attn_ln_w, L.attn_ln_b, L.qkv_w, L.qkv_b, 3 * D, D);
+      g.epi = EPI_QKV; g.y = t->qbuf; g.y_ld = D;
+      g.kcache = self_k_layer(t, l); g.vcache = self_v_layer(t, l); g.cache_bs = (int64_t)C * D; g.d_pos = t->d_pos; g.D = D;
+      g.lag = t->d_lag;
+      HIPCHK(launch_gemv(g, m->dtype, s));
+      HIPCHK(launch_attn_decode(self_attn_args(t, l, plan, 1), m->dtype, s));
     }
     if (t->fused_xout) out_done = true;       // attn.out + residual run as phase 0 of the cross-attention launch below
-    if (!out_done) {
-    memset(&g, 0, sizeof(g));
-    if (t->self_splits > 1) {
-      g.pro = PRO_COMBINE; g.part_o = t->part_o; g.part_ml = t->part_ml; g.splits = t->self_splits; g.H = H;
-    } else {
-      g.pro = PRO_PLAIN; g.x = t->att; g.x_ld = D; g.x_frag = frag_self;
-    }
-    g.W = L.out_w; g.bias = L.out_b; g.N = D; g.K = D; g.R = R;
-    g.epi = EPI_RESID; g.resid = xc; g.resid_ld = D;
-    HIPCHK(launch_gemv(g, m->dtype, s));
-    }
+    if (!out_done)
+      HIPCHK(gemv_resid(m, plain_proj(t, t->att, D, plan.frag_self, t->self_splits, R, L.out_w, L.out_b, D, D), xc, s));
     if (t->fused_xattn) {
       // LN -> cross query -> cross attention as ONE launch: the K/V stream starts at kernel entry, the projection runs
       // under it and reaches the K/V waves through tagged granules (xattn.hip)
       HIPCHK(launch_xattn8(xattn_args(t, l, 0, xc, t->fused_xout), s));
     } else {
-    // LN -> cross query
-    memset(&g, 0, sizeof(g));
-    g.pro = PRO_LN; g.xf = xc; g.xf_ld = D; g.ln_w = L.cross_ln_w; g.ln_b = L.cross_ln_b; g.ln_folded = (m->w.flags & WH_WEIGHTS_DEC_LN_FOLDED) ? 1 : 0;
-    g.W = L.cq_w; g.bias = L.cq_b; g.N = D; g.K = D; g.R = R;
-    g.epi = EPI_STORE; g.y = t->qbuf; g.y_ld = D;
-    HIPCHK(launch_gemv(g, m->dtype, s));
-    {
-      DecAttnArgs a; memset(&a, 0, sizeof(a));
-      a.q = t->qbuf; a.q_ld = D;
-      a.k = cross_layer(t, l); a.k_ld = 2 * D; a.k_bs = (int64_t)Ta * 2 * D;
-      a.v = (char*)cross_layer(t, l) + (size_t)D * es; a.v_ld = 2 * D; a.v_bs = a.k_bs;
-      a.H = H; a.R = R; a.kv_group = t->G; a.Tk = Ta; a.splits = t->cross_splits;
-      a.out = t->att; a.o_ld = D; a.part_o = t->part_o; a.part_ml = t->part_ml;
-      if (tail_merge) { a.merge_cnt = t->merge_cnt; a.o_frag = frag_att; }
-      if (t->cross_vt) {
-        a.vt = (char*)t->cross_vt + (size_t)l * t->B * D * t->vt_ld * es; a.vt_ld = t->vt_ld; a.vt_bs = (int64_t)D * t->vt_ld;
-      }
-      HIPCHK(launch_attn_decode(a, m->dtype, s));
+      // LN -> cross query
+      HIPCHK(gemv_store(m, ln_proj(m, xc, R, L.cross_ln_w, L.cross_ln_b, L.cq_w, L.cq_b, D, D), EPI_STORE, t->qbuf, D, false, s));
+      HIPCHK(launch_attn_decode(cross_attn_args(t, l, t->qbuf, R, t->G, t->cross_splits, &plan), m->dtype, s));
     }
-    }
-    memset(&g, 0, sizeof(g));
-    // 17+ rows (beam search): the projection runs as 16-row workgroups that would each merge their rows' partials
-    // again, so the merge is a launch of its own there (A/B: WH_NO_MERGE_KERNEL=1)
-    const bool merge_kernel = !WH_DEV_FLAG("WH_NO_MERGE_KERNEL");   // developer A/B switch
-    if (tail_merge) {                 // merged inside the attention launch by the last workgroup of each (row, head)
-      g.pro = PRO_PLAIN; g.x = t->att; g.x_ld = D; g.x_frag = frag_att;
-    } else if (t->cross_splits > 1 && R > 16 && m->dtype == WH_F16 && merge_kernel) {   // the fp32 engine keeps one code path
-      HIPCHK(launch_merge_partials(t->part_o, t->part_ml, t->cross_splits, R, H, t->att, D, m->dtype, s, frag_att));
-      g.pro = PRO_PLAIN; g.x = t->att; g.x_ld = D; g.x_frag = frag_att;
-    } else if (t->cross_splits > 1) {
-      g.pro = PRO_COMBINE; g.part_o = t->part_o; g.part_ml = t->part_ml; g.splits = t->cross_splits; g.H = H;
-    } else {
-      g.pro = PRO_PLAIN; g.x = t->att; g.x_ld = D;
-    }
-    g.W = L.cout_w; g.bias = L.cout_b; g.N = D; g.K = D; g.R = R;
-    g.epi = EPI_RESID; g.resid = xc; g.resid_ld = D;
-    HIPCHK(launch_gemv(g, m->dtype, s));
+    const int rc = launch_cross_out(t, plan, L, xc, s);
+    if (rc != WH_OK) return rc;
     // LN -> MLP
-    memset(&g, 0, sizeof(g));
-    g.pro = PRO_LN; g.xf = xc; g.xf_ld = D; g.ln_w = L.mlp_ln_w; g.ln_b = L.mlp_ln_b; g.ln_folded = (m->w.flags & WH_WEIGHTS_DEC_LN_FOLDED) ? 1 : 0;
-    g.W = L.fc1_w; g.bias = L.fc1_b; g.N = 4 * D; g.K = D; g.R = R;
-    g.epi = EPI_GELU; g.y = t->h; g.y_ld = 4 * D; g.y_frag = frag_mlp;
-    HIPCHK(launch_gemv(g, m->dtype, s));
-    memset(&g, 0, sizeof(g));
-    g.pro = PRO_PLAIN; g.x = t->h; g.x_ld = 4 * D; g.x_frag = frag_mlp;
-    g.W = L.fc2_w; g.bias = L.fc2_b; g.N = D; g.K = 4 * D; g.R = R;
-    g.epi = EPI_RESID; g.resid = xc; g.resid_ld = D;
-    HIPCHK(launch_gemv(g, m->dtype, s));
+    HIPCHK(gemv_store(m, ln_proj(m, xc, R, L.mlp_ln_w, L.mlp_ln_b, L.fc1_w, L.fc1_b, 4 * D, D), EPI_GELU, t->h, 4 * D, plan.frag_mlp, s));
+    HIPCHK(gemv_resid(m, plain_proj(t, t->h, 4 * D, plan.frag_mlp, 1, R, L.fc2_w, L.fc2_b, D, 4 * D), xc, s));
   }
-  {
-    GemvArgs g; memset(&g, 0, sizeof(g));
-    g.pro = PRO_LN; g.xf = xc; g.xf_ld = D; g.ln_w = m->w.dec_ln_w; g.ln_b = m->w.dec_ln_b;
-    g.W = m->w.tok_emb; g.bias = nullptr; g.N = V; g.K = D; g.R = R;
-    g.epi = EPI_F32; g.y = t->logits; g.y_ld = V;
-    g.bump = t->d_pos; g.bump_by = 1;         // the last kernel of the step advances the position counter
-    g.bump2 = t->d_tick;                      // ... and the step tick the granule tags of xattn.hip are made of
-    HIPCHK(launch_gemv(g, m->dtype, s));
-  }
+  GemvArgs g = logits_proj(m, xc, R, t->logits, V);
+  g.bump = t->d_pos; g.bump_by = 1;         // the last kernel of the step advances the position counter
+  g.bump2 = t->d_tick;                      // ... and the step tick the granule tags of xattn.hip are made of
+  HIPCHK(launch_gemv(g, m->dtype, s));
   return WH_OK;
 }
 
@@ -1176,11 +1183,7 @@ extern "C" int wh_task_rearrange(wh_task* t, const int32_t* source_indices, void
 // the cross K/V and the rows' lags are untouched.  The caller only ever sees the second result.
 static int handoff_fallback(wh_task* t, hipStream_t s) {
   t->fused_xattn = t->fused_sattn = t->fused_out = t->fused_xout = false;
-  for (int i = 0; i < 2; ++i) {
-    if (t->graph_exec[i]) { (void)hipGraphExecDestroy(t->graph_exec[i]); t->graph_exec[i] = nullptr; }
-    if (t->graph[i]) { (void)hipGraphDestroy(t->graph[i]); t->graph[i] = nullptr; }
-    t->steps_eager[i] = 0;
-  }
+  drop_step_graphs(t);
   HIPCHK(hipMemsetAsync(t->d_pos, 0, 4, s));
   t->pos = 0;
   t->handoff_fallbacks++;
@@ -1209,6 +1212,60 @@ static int event_reached(hipEvent_t e, bool block) {
   return WH_ERR_HIP;
 }
 
+// after a `leaders` prefill: cache rows 0 .. B-1 hold the T0 prompt positions of the B segments and logits rows 0 .. B-1
+// their selected logits; row b goes to rows b G .. b G + G - 1.  Descending b: the destination rows of segment b only
+// overlap source rows of segments above b, which have been replicated by then.
+static int replicate_leader_rows(wh_task* t, int T0, float* logits, int n_sel, hipStream_t s) {
+  const wh_dims& d = t->m->d;
+  const size_t es = t->m->esize;
+  const int64_t row_bytes = (int64_t)d.n_text_ctx * d.n_text_state * es;
+  const int64_t layer_bytes = (int64_t)t->R * row_bytes;
+  for (int b = t->B - 1; b >= 0; --b) {
+    HIPCHK(launch_replicate_row(t->self_k, layer_bytes, d.n_text_layer, row_bytes, b, b * t->G, t->G,
+                                (int64_t)T0 * d.n_text_state * es, s));
+    HIPCHK(launch_replicate_row(t->self_v, layer_bytes, d.n_text_layer, row_bytes, b, b * t->G, t->G,
+                                (int64_t)T0 * d.n_text_state * es, s));
+    if (logits)
+      HIPCHK(launch_replicate_row(logits, 0, 1, (int64_t)n_sel * d.n_vocab * 4, b, b * t->G, t->G,
+                                  (int64_t)n_sel * d.n_vocab * 4, s));
+  }
+  return WH_OK;
+}
+
+// the rows and sampling rules the greedy sampler and the beam update share (SampleArgs / BeamArgs name them alike)
+template <class Args>
+static void set_sampling_rules(Args& a, const wh_task* t, const wh_loop* L) {
+  const wh_greedy_params* p = &L->bp.rules;
+  a.R = t->R; a.V = t->m->d.n_vocab; a.token_stride = L->token_stride; a.d_ntok = t->d_pos; a.lag = t->d_lag;
+  a.sample_begin = p->sample_begin; a.eot = p->eot; a.timestamp_begin = p->timestamp_begin; a.no_timestamps = p->no_timestamps;
+  a.max_initial_ts = p->max_initial_timestamp_index; a.suppress_blank = p->suppress_blank;
+  a.blank_token = p->blank_token; a.suppress_mask = p->suppress_mask; a.sum_logprobs = L->sum_logprobs;
+}
+
+// the prompt pass of a fused loop: t->logits holds *n_sel rows of logits per task row afterwards, the last of them the
+// first decision's.  leaders: the G beams of a segment hold the same prompt — one row per segment through the decoder, then
+// replicate
+static int loop_prompt_pass(wh_task* t, bool leaders, int* n_sel_out) {
+  wh_loop* L = t->loop;
+  hipStream_t s = L->s;
+  const int V = t->m->d.n_vocab, R = t->R, T0 = L->bp.rules.sample_begin;
+  // hand-off time-outs are judged per call: the counter as it stands when this call's work starts (stream-ordered copy)
+  // is the baseline, so time-outs of earlier host-driven wh_task_step calls on a cached task do not trigger a fallback here
+  HIPCHK(hipMemcpyAsync(t->h_poll + t->B + HP_ERR0, t->d_err, 4, hipMemcpyDeviceToHost, s));
+
+  int32_t sel[2]; int n_sel;
+  const bool want_ns = L->no_speech_token >= 0 && L->no_speech_probs != nullptr;
+  if (want_ns && L->sot_index != T0 - 1) { sel[0] = L->sot_index; sel[1] = T0 - 1; n_sel = 2; }
+  else { sel[0] = T0 - 1; n_sel = 1; }
+  int rc = prefill_impl(t, L->tokens, L->token_stride, T0, sel, n_sel, t->logits, V, s, leaders);
+  if (rc != WH_OK) return rc;
+  if (leaders) { rc = replicate_leader_rows(t, T0, t->logits, n_sel, s); if (rc != WH_OK) return rc; }
+  if (want_ns) HIPCHK(launch_no_speech(t->logits, (int64_t)n_sel * V, R, V, L->no_speech_token, L->no_speech_probs, s));
+  HIPCHK(hipMemsetAsync(L->sum_logprobs, 0, (size_t)R * 4, s));
+  *n_sel_out = n_sel;
+  return WH_OK;
+}
+
 static int greedy_start(wh_task* t) {
   wh_loop* L = t->loop;
   hipStream_t s = L->s;
@@ -1216,26 +1273,15 @@ static int greedy_start(wh_task* t) {
   const wh_dims& d = t->m->d;
   const int V = d.n_vocab, R = t->R, T0 = p->sample_begin;
   int* hp = t->h_poll + t->B;
-  // hand-off time-outs are judged per call: the counter as it stands when this call's work starts (stream-ordered copy)
-  // is the baseline, so time-outs of earlier host-driven wh_task_step calls on a cached task do not trigger a fallback here
-  HIPCHK(hipMemcpyAsync(hp + HP_ERR0, t->d_err, 4, hipMemcpyDeviceToHost, s));
-
-  int32_t sel[2]; int n_sel;
-  const bool want_ns = L->no_speech_token >= 0 && L->no_speech_probs != nullptr;
-  if (want_ns && L->sot_index != T0 - 1) { sel[0] = L->sot_index; sel[1] = T0 - 1; n_sel = 2; }
-  else { sel[0] = T0 - 1; n_sel = 1; }
-  int rc = prefill_impl(t, L->tokens, L->token_stride, T0, sel, n_sel, t->logits, V, s);
+  int n_sel;
+  int rc = loop_prompt_pass(t, false, &n_sel);
   if (rc != WH_OK) return rc;
-  if (want_ns) HIPCHK(launch_no_speech(t->logits, (int64_t)n_sel * V, R, V, L->no_speech_token, L->no_speech_probs, s));
-  HIPCHK(hipMemsetAsync(L->sum_logprobs, 0, (size_t)R * 4, s));
   hp[HP_ALIVE_INIT] = T0 - 1;                          // pinned: read when the copy executes; rewritten only by a later loop
   HIPCHK(hipMemcpyAsync(t->d_alive, hp + HP_ALIVE_INIT, 4, hipMemcpyHostToDevice, s));
 
   SampleArgs& sa = L->sa; memset(&sa, 0, sizeof(sa));
-  sa.R = R; sa.V = V; sa.tokens = L->tokens; sa.token_stride = L->token_stride; sa.d_ntok = t->d_pos; sa.lag = t->d_lag;
-  sa.sample_begin = T0; sa.eot = p->eot; sa.timestamp_begin = p->timestamp_begin; sa.no_timestamps = p->no_timestamps;
-  sa.max_initial_ts = p->max_initial_timestamp_index; sa.suppress_blank = p->suppress_blank;
-  sa.blank_token = p->blank_token; sa.suppress_mask = p->suppress_mask; sa.sum_logprobs = L->sum_logprobs;
+  set_sampling_rules(sa, t, L);
+  sa.tokens = L->tokens;
   sa.step_tokens = t->step_tokens; sa.d_alive_step = t->d_alive; sa.partials = t->samp_part;
   sa.row_state = t->samp_state;
   HIPCHK(hipMemsetAsync(t->samp_state, 0, (size_t)R * 16, s));
@@ -1267,26 +1313,6 @@ static int greedy_start(wh_task* t) {
   return WH_OK;
 }
 
-// after a `leaders` prefill: cache rows 0 .. B-1 hold the T0 prompt positions of the B segments and logits rows 0 .. B-1
-// their selected logits; row b goes to rows b G .. b G + G - 1.  Descending b: the destination rows of segment b only
-// overlap source rows of segments above b, which have been replicated by then.
-static int replicate_leader_rows(wh_task* t, int T0, float* logits, int n_sel, hipStream_t s) {
-  const wh_dims& d = t->m->d;
-  const size_t es = t->m->esize;
-  const int64_t row_bytes = (int64_t)d.n_text_ctx * d.n_text_state * es;
-  const int64_t layer_bytes = (int64_t)t->R * row_bytes;
-  for (int b = t->B - 1; b >= 0; --b) {
-    HIPCHK(launch_replicate_row(t->self_k, layer_bytes, d.n_text_layer, row_bytes, b, b * t->G, t->G,
-                                (int64_t)T0 * d.n_text_state * es, s));
-    HIPCHK(launch_replicate_row(t->self_v, layer_bytes, d.n_text_layer, row_bytes, b, b * t->G, t->G,
-                                (int64_t)T0 * d.n_text_state * es, s));
-    if (logits)
-      HIPCHK(launch_replicate_row(logits, 0, 1, (int64_t)n_sel * d.n_vocab * 4, b, b * t->G, t->G,
-                                  (int64_t)n_sel * d.n_vocab * 4, s));
-  }
-  return WH_OK;
-}
-
 // one BeamSearchDecoder.update on the device (3 launches) + rearrange_kv_cache (decoding.py:172-176): new beam i continues
 // the cache of row src[i]
 static int beam_update(wh_task* t, const float* logits, int64_t logits_ld, int first) {
@@ -1315,29 +1341,18 @@ static int beam_start(wh_task* t) {
   const wh_greedy_params* p = &L->bp.rules;
   const wh_dims& d = t->m->d;
   const int V = d.n_vocab, R = t->R, B = t->B, G = t->G, T0 = p->sample_begin;
-  int* hp = t->h_poll + B;
-  HIPCHK(hipMemcpyAsync(hp + HP_ERR0, t->d_err, 4, hipMemcpyDeviceToHost, s));      // time-out counter at call entry (see greedy_start)
-
-  int32_t sel[2]; int n_sel;
-  const bool want_ns = L->no_speech_token >= 0 && L->no_speech_probs != nullptr;
-  if (want_ns && L->sot_index != T0 - 1) { sel[0] = L->sot_index; sel[1] = T0 - 1; n_sel = 2; }
-  else { sel[0] = T0 - 1; n_sel = 1; }
   // the G beams of a segment hold the same prompt: one row per segment through the decoder, then replicate (A/B:
   // WH_BEAM_FULL_PREFILL=1 feeds all R rows as the reference does)
   const bool leaders = !WH_DEV_FLAG("WH_BEAM_FULL_PREFILL");
-  int rc = prefill_impl(t, L->tokens, L->token_stride, T0, sel, n_sel, t->logits, V, s, leaders);
+  int n_sel;
+  int rc = loop_prompt_pass(t, leaders, &n_sel);
   if (rc != WH_OK) return rc;
-  if (leaders) { rc = replicate_leader_rows(t, T0, t->logits, n_sel, s); if (rc != WH_OK) return rc; }
-  if (want_ns) HIPCHK(launch_no_speech(t->logits, (int64_t)n_sel * V, R, V, L->no_speech_token, L->no_speech_probs, s));
-  HIPCHK(hipMemsetAsync(L->sum_logprobs, 0, (size_t)R * 4, s));
   HIPCHK(hipMemsetAsync(L->fin_count, 0, (size_t)B * 4, s));
   HIPCHK(hipMemsetAsync(t->beam_flags, 0, (2 * (size_t)B + 1) * 4, s));
 
   BeamArgs& a = L->ba; memset(&a, 0, sizeof(a));
-  a.R = R; a.V = V; a.G = G; a.K = G + 1; a.token_stride = L->token_stride; a.d_ntok = t->d_pos; a.lag = t->d_lag;
-  a.sample_begin = T0; a.eot = p->eot; a.timestamp_begin = p->timestamp_begin; a.no_timestamps = p->no_timestamps;
-  a.max_initial_ts = p->max_initial_timestamp_index; a.suppress_blank = p->suppress_blank;
-  a.blank_token = p->blank_token; a.suppress_mask = p->suppress_mask; a.sum_logprobs = L->sum_logprobs;
+  set_sampling_rules(a, t, L);
+  a.G = G; a.K = G + 1;
   beam_scratch_carve(a, t->beam_scratch, R, V);
   a.fin_tok = L->fin_tokens; a.fin_len = L->fin_len; a.fin_score = L->fin_scores; a.fin_count = L->fin_count;
   a.max_candidates = L->bp.max_candidates;
@@ -1563,15 +1578,16 @@ static int bench_issue(wh_task* t, int kind, int iters, double* bytes_per_launch
   hipStream_t s = (hipStream_t)stream_;
   const wh_model* m = t->m;
   const wh_dims& d = m->d;
-  const int D = d.n_text_state, H = d.n_text_head, C = d.n_text_ctx, Ta = d.n_audio_ctx, V = d.n_vocab;
+  const int D = d.n_text_state, Ta = d.n_audio_ctx, V = d.n_vocab;
   const int R = t->R, Ln = d.n_text_layer;
   const double es = m->esize;
-  const StepPlan plan = step_plan(t);            // the kernels are timed in the form the step launches them in
+  // the kernels are timed in the form the step launches them in: the same builders, with epilogues that leave the task's
+  // state alone (plain stores into t->qkv / t->att / t->qbuf, no cache append, no residual add, no position bump)
+  const StepPlan plan = step_plan(t);
   double bytes = 0;
   for (int i = 0; i < iters; ++i) {
     const int l = i % Ln;
     const wh_layer_weights& L = m->dec[l];
-    GemvArgs g; memset(&g, 0, sizeof(g));
     switch (kind) {
       case 0: {
         int rc = step_launch(t, s);
@@ -1589,14 +1605,7 @@ static int bench_issue(wh_task* t, int kind, int iters, double* bytes_per_launch
         if (i == iters - 1) HIPCHK(launch_add_int(t->d_tick, iters, s));
         bytes = (double)t->B * 2.0 * Ta * D * es + (t->fused_xout ? 2.0 : 1.0) * D * D * es;
       } else {
-        DecAttnArgs a; memset(&a, 0, sizeof(a));
-        a.q = t->qbuf; a.q_ld = D;
-        a.k = cross_layer(t, l); a.k_ld = 2 * D; a.k_bs = (int64_t)Ta * 2 * D;
-        a.v = (char*)cross_layer(t, l) + (size_t)D * m->esize; a.v_ld = 2 * D; a.v_bs = a.k_bs;
-        a.H = H; a.R = R; a.kv_group = t->G; a.Tk = Ta; a.splits = t->cross_splits;
-        a.out = t->att; a.o_ld = D; a.part_o = t->part_o; a.part_ml = t->part_ml;
-        if (plan.tail_merge) { a.merge_cnt = t->merge_cnt; a.o_frag = plan.frag_att; }
-        HIPCHK(launch_attn_decode(a, m->dtype, s));
+        HIPCHK(launch_attn_decode(cross_attn_args(t, l, t->qbuf, R, t->G, t->cross_splits, &plan), m->dtype, s));
         bytes = (double)t->B * 2.0 * Ta * D * es;
       } break;
       case 2: if (t->fused_sattn) {
@@ -1604,48 +1613,27 @@ static int bench_issue(wh_task* t, int kind, int iters, double* bytes_per_launch
         if (i == iters - 1) HIPCHK(launch_add_int(t->d_tick, iters, s));
         bytes = (double)R * t->pos * 2.0 * D * es + (t->fused_out ? 4.0 : 3.0) * D * D * es;
       } else {
-        DecAttnArgs a; memset(&a, 0, sizeof(a));
-        a.q = t->qbuf; a.q_ld = D;
-        a.k = self_k_layer(t, l); a.k_ld = D; a.k_bs = (int64_t)C * D;
-        a.v = self_v_layer(t, l); a.v_ld = D; a.v_bs = (int64_t)C * D;
-        a.H = H; a.R = R; a.kv_group = 1; a.d_len = t->d_pos; a.len_plus = 0; a.splits = t->self_splits;
-        a.out = t->att; a.o_ld = D; a.o_frag = plan.frag_self; a.part_o = t->part_o; a.part_ml = t->part_ml;
-        HIPCHK(launch_attn_decode(a, m->dtype, s));
+        HIPCHK(launch_attn_decode(self_attn_args(t, l, plan, 0), m->dtype, s));     // the keys cached so far: nothing is appended here
         bytes = (double)R * t->pos * 2.0 * D * es;
       } break;
       case 3:
-        g.pro = PRO_LN; g.xf = t->x; g.xf_ld = D; g.ln_w = L.attn_ln_w; g.ln_b = L.attn_ln_b; g.ln_folded = (m->w.flags & WH_WEIGHTS_DEC_LN_FOLDED) ? 1 : 0;
-        g.W = L.qkv_w; g.bias = L.qkv_b; g.N = 3 * D; g.K = D; g.R = R;
-        g.epi = EPI_STORE; g.y = t->qkv; g.y_ld = 3 * D;
-        HIPCHK(launch_gemv(g, m->dtype, s));
+        HIPCHK(gemv_store(m, ln_proj(m, t->x, R, L.attn_ln_w, L.attn_ln_b, L.qkv_w, L.qkv_b, 3 * D, D), EPI_STORE, t->qkv, 3 * D, false, s));
         bytes = 3.0 * D * D * es;
         break;
       case 4:
-        g.pro = PRO_LN; g.xf = t->x; g.xf_ld = D; g.ln_w = L.mlp_ln_w; g.ln_b = L.mlp_ln_b; g.ln_folded = (m->w.flags & WH_WEIGHTS_DEC_LN_FOLDED) ? 1 : 0;
-        g.W = L.fc1_w; g.bias = L.fc1_b; g.N = 4 * D; g.K = D; g.R = R;
-        g.epi = EPI_GELU; g.y = t->h; g.y_ld = 4 * D; g.y_frag = plan.frag_mlp;
-        HIPCHK(launch_gemv(g, m->dtype, s));
+        HIPCHK(gemv_store(m, ln_proj(m, t->x, R, L.mlp_ln_w, L.mlp_ln_b, L.fc1_w, L.fc1_b, 4 * D, D), EPI_GELU, t->h, 4 * D, plan.frag_mlp, s));
         bytes = 4.0 * D * D * es;
         break;
       case 5:
-        g.pro = PRO_PLAIN; g.x = t->h; g.x_ld = 4 * D; g.x_frag = plan.frag_mlp;
-        g.W = L.fc2_w; g.bias = L.fc2_b; g.N = D; g.K = 4 * D; g.R = R;
-        g.epi = EPI_STORE; g.y = t->att; g.y_ld = D;
-        HIPCHK(launch_gemv(g, m->dtype, s));
+        HIPCHK(gemv_store(m, plain_proj(t, t->h, 4 * D, plan.frag_mlp, 1, R, L.fc2_w, L.fc2_b, D, 4 * D), EPI_STORE, t->att, D, false, s));
         bytes = 4.0 * D * D * es;
         break;
       case 6:
-        g.pro = PRO_LN; g.xf = t->x; g.xf_ld = D; g.ln_w = m->w.dec_ln_w; g.ln_b = m->w.dec_ln_b;
-        g.W = m->w.tok_emb; g.N = V; g.K = D; g.R = R;
-        g.epi = EPI_F32; g.y = t->logits; g.y_ld = V;
-        HIPCHK(launch_gemv(g, m->dtype, s));
+        HIPCHK(launch_gemv(logits_proj(m, t->x, R, t->logits, V), m->dtype, s));
         bytes = (double)V * D * es + (double)R * V * 4.0;
         break;
       case 7:
-        g.pro = PRO_PLAIN; g.x = t->att; g.x_ld = D; g.x_frag = plan.frag_self;
-        g.W = L.out_w; g.bias = L.out_b; g.N = D; g.K = D; g.R = R;
-        g.epi = EPI_STORE; g.y = t->qbuf; g.y_ld = D;
-        HIPCHK(launch_gemv(g, m->dtype, s));
+        HIPCHK(gemv_store(m, plain_proj(t, t->att, D, plan.frag_self, 1, R, L.out_w, L.out_b, D, D), EPI_STORE, t->qbuf, D, false, s));
         bytes = 1.0 * D * D * es;
         break;
       default: return WH_ERR_ARG;
@@ -1709,8 +1697,8 @@ extern "C" int wh_task_cross_qk(wh_task* t, int row, const int32_t* layers, cons
     const int l = layers[i], h = heads[i];
     if (l < 0 || l >= d.n_text_layer || h < 0 || h >= d.n_text_head) return WH_ERR_ARG;
     const char* q = (const char*)t->qcap + ((((size_t)l * t->R + row) * C) + tok_begin) * D * es;
-    const char* k = (const char*)cross_layer(t, l) + (size_t)(row / t->G) * Ta * 2 * D * es;
-    HIPCHK(launch_cross_qk(q, D, k, 2 * D, h, n_tok, Ta, out + (size_t)i * n_tok * Ta, t->m->dtype, s));
+    const char* k = (const char*)cross_layer(t, l) + (size_t)(row / t->G) * cross_bs(t) * es;
+    HIPCHK(launch_cross_qk(q, D, k, cross_ld(t), h, n_tok, Ta, out + (size_t)i * n_tok * Ta, t->m->dtype, s));
   }
   return WH_OK;
 }
@@ -1760,10 +1748,8 @@ extern "C" int wh_task_align_batch(wh_task* t, const int32_t* layers, const int3
   HIPCHK(hipMemcpyAsync(ints, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(hipStreamSynchronize(s));       // `h` is host stack memory
   const int *d_ntok = ints, *d_nfr = ints + R, *d_layers = ints + 2 * R, *d_heads = ints + 2 * R + n_pairs;
-  const size_t es = t->m->esize;
-  (void)es;
-  HIPCHK(launch_cross_qk_batch(t->qcap, (int64_t)R * C * D, (int64_t)C * D, D, t->cross_kv, (int64_t)t->B * Ta * 2 * D,
-                               (int64_t)Ta * 2 * D, t->G, d_layers, d_heads, n_pairs, d_ntok, R, Tmax, Ta, qk,
+  HIPCHK(launch_cross_qk_batch(t->qcap, (int64_t)R * C * D, (int64_t)C * D, D, t->cross_kv, t->B * cross_bs(t),
+                               cross_bs(t), t->G, d_layers, d_heads, n_pairs, d_ntok, R, Tmax, Ta, qk,
                                t->m->dtype, s));
   HIPCHK(launch_align_batch(qk, d_ntok, d_nfr, R, n_pairs, Tmax, Ta, Fmax, width, row_begin, 1, qk_scale, cost_out, Nmax, w, s));
   HIPCHK(launch_dtw_batch(cost_out, d_ntok, d_nfr, R, Tmax, Fmax, row_begin, 1, Nmax, trace_out, trace_stride, s));
@@ -1811,8 +1797,8 @@ extern "C" int wh_task_align_open_batch(wh_task* t, const int32_t* layers, const
   HIPCHK(hipStreamSynchronize(s));       // `h`, `h2` are host stack memory
   const int *d_ntok = ints, *d_nfr = ints + R, *d_layers = ints + 2 * R, *d_heads = ints + 2 * R + n_pairs;
   const int *d_rows = ints2, *d_closed = ints2 + R;
-  HIPCHK(launch_cross_qk_batch(t->qcap, (int64_t)R * C * D, (int64_t)C * D, D, t->cross_kv, (int64_t)t->B * Ta * 2 * D,
-                               (int64_t)Ta * 2 * D, t->G, d_layers, d_heads, n_pairs, d_ntok, R, Tmax, Ta, qk,
+  HIPCHK(launch_cross_qk_batch(t->qcap, (int64_t)R * C * D, (int64_t)C * D, D, t->cross_kv, t->B * cross_bs(t),
+                               cross_bs(t), t->G, d_layers, d_heads, n_pairs, d_ntok, R, Tmax, Ta, qk,
                                t->m->dtype, s));
   HIPCHK(launch_align_batch(qk, d_ntok, d_nfr, R, n_pairs, Tmax, Ta, Fmax, width, row_begin, 1, qk_scale, cost_out, Nmax, w, s));
   HIPCHK(launch_dtw_open_batch(cost_out, d_rows, d_nfr, d_closed, R, Nmax, Fmax, end_slack, trace_out, trace_stride,
