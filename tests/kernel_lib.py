@@ -17,6 +17,7 @@ SIGNATURES = {
     "wht_clear_form": (None, []),
     "wht_attn_decode_capacity": (_I, [_I]),
     "wht_gemv8_will_run": (_I, [_I, _I, _I, _I]),
+    "wht_gemv_family": (ctypes.c_char_p, [_I, _I, _I, _I, _I, _I, _L, _I, _I, _I, _I, _I, _I]),
     "wht_gemv": (_I, [_I, _I, _P, _L, _P, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L,
                       _P, _P, _L, _P, _I, _P, _P, _I, _P, _P]),
     "wht_merge_partials": (_I, [_P, _P, _I, _I, _I, _P, _L, _I, _I, _P]),
@@ -61,3 +62,27 @@ def lib():
 
 def last_form() -> str:
     return lib().wht_last_form().decode()
+
+
+def gemv_family(dtype, pro, epi, R, N, K, ld, ln_folded, has_bias, splits, H, frag) -> str:
+    """the family launch_gemv picks for the launch _gemv_case (test_kernel_parity_gpu.py) makes of these arguments, asked of
+    wht_gemv_family (gemv.hip: pick_family) — nothing is launched; "" = refused.  frag: x_frag where PRO_PLAIN (0), y_frag where
+    EPI_STORE (0) / EPI_GELU (3)"""
+    return lib().wht_gemv_family(dtype, pro, epi, R, N, K, ld, ln_folded, has_bias, splits, H, int(bool(frag) and pro == 0),
+                                 int(bool(frag) and epi in (0, 3))).decode()
+
+
+def family_of_tag(tag: str) -> str:
+    """the family of a gemv form tag (kernels.h: g_form)"""
+    if tag.startswith("gemv8/"):
+        return "gemv8"
+    if tag in ("rows48", "rows48_stream"):
+        return tag
+    if tag.startswith("rows16_mf<"):
+        return "rows16_mf"
+    for head in ("rt<", "stream<"):
+        if tag.startswith(head):
+            rt = tag[len(head):tag.index(">")].split(",")[1]
+            assert rt in ("4", "8"), tag
+            return "rt" + rt
+    raise AssertionError(f"not a gemv form tag: {tag!r}")

@@ -35,7 +35,7 @@ import math
 import pytest
 import torch
 
-from kernel_lib import hipErrorInvalidValue, hipSuccess, last_form, lib
+from kernel_lib import family_of_tag, gemv_family, hipErrorInvalidValue, hipSuccess, last_form, lib
 from parity_ref import (C_ATT_MFMA, C_ATT_VALU, C_DOT, F16, F32, GUARD, Buf, _dev, _flip_slack, _merge_ref,  # noqa: F401
                         _r, _stream, _tdt, _ulp, attn_bound, attn_ref, ln_rows_ref)
 
@@ -171,6 +171,7 @@ def _gemv_case(dtype, R, N, K, pro=PLAIN, epi=STORE, bias=True, ln_folded=True, 
     torch.cuda.synchronize()
     form = last_form()
     assert form, "no form tag"
+    assert gemv_family(dtype, pro, epi, R, N, K, x_ld, int(ln_folded), int(bias), splits, H or 0, frag) == family_of_tag(form)
     assert bump.tolist() == [8, 8], f"{form}: bump / bump2 moved {bump.tolist()} (want [8, 8])"
     for b in (xbuf, xf, po, pml):                                  # inputs are not written
         if b is not None:

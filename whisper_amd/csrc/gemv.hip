@@ -531,24 +531,9 @@ hipError_t launch_rt(const whk::GemvArgs& a, hipStream_t stream) {
     if ((nblk8 + 3) / 4 <= 10) return launch_pro<T, RT, 8, false, 4, 1>(a, 1, stream);
     return launch_pro<T, RT, 8, true, 4, 1>(a, 1, stream);
   }
-#ifdef WH_PROBE   // MFMA forms: measured, not faster on these latency-bound launches (profiles/r01_gemv_shape_sweep.txt);
-                  // compiled only into tools/probe_decode so the comparison stays reproducible
-  if constexpr (sizeof(T) == 2 && RT >= 8) {
-    if (a.K % 32 == 0) {
-      switch (force) {
-        case 11: return launch_pro<T, RT, 4, false, 4, 1, true>(a, 1, stream);
-        case 12: return launch_pro<T, RT, 4, false, 8, 1, true>(a, 1, stream);
-        case 13: return launch_pro<T, RT, 4, false, 8, 2, true>(a, 1, stream);
-        case 14: return launch_pro<T, RT, 4, false, 16, 4, true>(a, 1, stream);
-        case 15: return launch_pro<T, RT, 4, false, 16, 1, true>(a, 1, stream);
-        case 16: return launch_pro<T, RT, 4, false, 16, 2, true>(a, 1, stream);
-        case 17: return launch_pro<T, RT, 4, true, 4, 1, true>(a, ((a.N + 15) / 16 + 1023) / 1024, stream);
-        default: break;
-      }
-    }
-  }
-#endif
-#ifdef WH_PROBE
+#ifdef WH_PROBE   // the forced shapes of tools/probe_decode, compiled only there so that the comparison stays reproducible
+  constexpr bool MF = sizeof(T) == 2 && RT >= 8;         // the MFMA forms (11..17): fp16 row tiles of 8, K a multiple of 32
+  if (force >= 11 && (!MF || a.K % 32 != 0)) return hipErrorInvalidValue;
   switch (force) {
     case 1: return launch_pro<T, RT, 8, false, 4, 1>(a, 1, stream);
     case 2: return launch_pro<T, RT, 16, false, 4, 1>(a, 1, stream);
@@ -558,11 +543,18 @@ hipError_t launch_rt(const whk::GemvArgs& a, hipStream_t stream) {
     case 6: return launch_pro<T, RT, 8, false, 8, 2>(a, 1, stream);
     case 7: return launch_pro<T, RT, 8, false, 16, 2>(a, 1, stream);
     case 8: return launch_pro<T, RT, 8, false, 16, 4>(a, 1, stream);
-    default: return hipErrorInvalidValue;
+    // MFMA forms: measured, not faster on these latency-bound launches (profiles/r01_gemv_shape_sweep.txt)
+    case 11: if constexpr (MF) return launch_pro<T, RT, 4, false, 4, 1, true>(a, 1, stream); break;
+    case 12: if constexpr (MF) return launch_pro<T, RT, 4, false, 8, 1, true>(a, 1, stream); break;
+    case 13: if constexpr (MF) return launch_pro<T, RT, 4, false, 8, 2, true>(a, 1, stream); break;
+    case 14: if constexpr (MF) return launch_pro<T, RT, 4, false, 16, 4, true>(a, 1, stream); break;
+    case 15: if constexpr (MF) return launch_pro<T, RT, 4, false, 16, 1, true>(a, 1, stream); break;
+    case 16: if constexpr (MF) return launch_pro<T, RT, 4, false, 16, 2, true>(a, 1, stream); break;
+    case 17: if constexpr (MF) return launch_pro<T, RT, 4, true, 4, 1, true>(a, ((a.N + 15) / 16 + 1023) / 1024, stream); break;
+    default: break;
   }
-#else
-  return hipErrorInvalidValue;
 #endif
+  return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -572,21 +564,18 @@ hipError_t launch_rt(const whk::GemvArgs& a, hipStream_t stream) {
 // ---------------------------------------------------------------------------------------------------------------
 template <typename T>
 hipError_t launch_rows16_mf(const whk::GemvArgs& a, hipStream_t stream) {
-  if constexpr (sizeof(T) == 2) {
-    const int ngroups16 = (a.N + 15) / 16;
-    const int nks = a.K / 32;
-    if (nks > 40) {                                    // D x 4D: K split 16 ways, x fills the LDS exactly at K = 5120
-      if ((nks + 15) / 16 <= 10) return launch_pro<T, 16, 4, false, 16, 1, true>(a, 1, stream);
-      return hipErrorInvalidValue;
-    }
-    if (ngroups16 > 1024) return launch_pro<T, 16, 4, true, 4, 1, true>(a, (ngroups16 + 1023) / 1024, stream);
-    if (a.pro == whk::PRO_LN && ngroups16 >= 300) return launch_pro<T, 16, 4, false, 16, 4, true>(a, 1, stream);
-    if (a.pro == whk::PRO_LN && ngroups16 >= 200) return launch_pro<T, 16, 4, false, 8, 2, true>(a, 1, stream);
-    if (a.pro != whk::PRO_PLAIN) return launch_pro<T, 16, 4, false, 8, 1, true>(a, 1, stream);
-    return launch_pro<T, 16, 4, false, 4, 1, true>(a, 1, stream);
-  } else {
+  static_assert(sizeof(T) == 2, "fp16 only");
+  const int ngroups16 = (a.N + 15) / 16;
+  const int nks = a.K / 32;
+  if (nks > 40) {                                    // D x 4D: K split 16 ways, x fills the LDS exactly at K = 5120
+    if ((nks + 15) / 16 <= 10) return launch_pro<T, 16, 4, false, 16, 1, true>(a, 1, stream);
     return hipErrorInvalidValue;
   }
+  if (ngroups16 > 1024) return launch_pro<T, 16, 4, true, 4, 1, true>(a, (ngroups16 + 1023) / 1024, stream);
+  if (a.pro == whk::PRO_LN && ngroups16 >= 300) return launch_pro<T, 16, 4, false, 16, 4, true>(a, 1, stream);
+  if (a.pro == whk::PRO_LN && ngroups16 >= 200) return launch_pro<T, 16, 4, false, 8, 2, true>(a, 1, stream);
+  if (a.pro != whk::PRO_PLAIN) return launch_pro<T, 16, 4, false, 8, 1, true>(a, 1, stream);
+  return launch_pro<T, 16, 4, false, 4, 1, true>(a, 1, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1173,7 +1162,6 @@ hipError_t launch_gemv8_pro(const whk::GemvArgs& a, hipStream_t stream) {
     }
     return launch_gemv8_cfg<PRO, 1, 4, CSm, 0>(a, fw, stream);
   } else {
-    if (nblk > 20) return hipErrorNotSupported;              // the prologue waves cover K <= 1280
     if constexpr (PRO == whk::PRO_LN) {
       // 3 slots (4D x D of large-v3: 256 workgroups x 20 features).  Up to 8 rows: 12 weight waves + 4 LayerNorm waves of 2 rows.
       // From 9 rows on the 4 LayerNorm waves (6 rows each at 24 rows, two round trips) were the launch's long pole (9280 of its
@@ -1189,46 +1177,36 @@ hipError_t launch_gemv8_pro(const whk::GemvArgs& a, hipStream_t stream) {
   }
 }
 
-static bool gemv8_covers(int N, int K, int pro) {
-  if (K % 64 != 0) return false;
-  const int nblk = K / 64;
-  if (nblk > 20 ? (nblk + 15) / 16 > 5 : (nblk + 3) / 4 > 5) return false;
-  if (pro != whk::PRO_PLAIN && nblk > 20) return false;
-  if ((int64_t)N * K >= (1ll << 31)) return false;
-  return true;
-}
-bool gemv8_enabled() {
-  return !WH_DEV_FLAG("WH_GEMV_DOT2");      // developer switch: the round-1 v_dot2 kernels instead
-}
-
-// returns hipErrorNotSupported when the shape / mode is not covered (the caller falls back to the v_dot2 kernels)
-hipError_t launch_gemv8(const whk::GemvArgs& a, hipStream_t stream) {
-  if (!gemv8_enabled() || a.variant != 0) return hipErrorNotSupported;
-  if (a.K % 64 != 0) return hipErrorNotSupported;
+// Everything gemv8_kernel covers, the one list: pick_family asks it before launch_gemv8 runs, gemv8_will_run asks it for
+// api.cpp::step_plan.  fp16, 1..96 rows (row tiles of 8 x 1 / 2 / 3 / 6), K a multiple of 64 in at most 5 wave-loads per
+// K split (4 splits up to K = 1280, 16 beyond, PRO_PLAIN only: the prologue waves cover K <= 1280).
+bool gemv8_applies(const whk::GemvArgs& a) {
+  if (WH_DEV_FLAG("WH_GEMV_DOT2")) return false;             // developer switch: the round-1 v_dot2 kernels instead
+  if (a.variant != 0 || a.R < 1 || a.R > 96 || a.K % 64 != 0) return false;
   const int nblk = a.K / 64;
-  if (nblk > 20 ? (nblk + 15) / 16 > 5 : (nblk + 3) / 4 > 5) return hipErrorNotSupported;
-  if (a.epi == whk::EPI_F32 && a.N > 16384) return hipErrorNotSupported;      // logits: the streaming kernel
-  if ((int64_t)a.N * a.K >= (1ll << 31)) return hipErrorNotSupported;         // 32-bit lane offsets
+  if (nblk > 20 && (a.pro != whk::PRO_PLAIN || (nblk + 15) / 16 > 5)) return false;
+  if (a.epi == whk::EPI_F32 && a.N > 16384) return false;    // logits: the streaming kernels
+  if ((int64_t)a.N * a.K >= (1ll << 31)) return false;       // 32-bit lane offsets, here and on R * ld below
   switch (a.pro) {
-    case whk::PRO_PLAIN:
-      if (a.x_ld % 8 != 0 || (int64_t)a.R * a.x_ld >= (1ll << 30)) return hipErrorNotSupported;
-      return launch_gemv8_pro<whk::PRO_PLAIN, 1>(a, stream);
-    case whk::PRO_LN:
-      if (!a.ln_folded || a.xf_ld % 4 != 0 || (int64_t)a.R * a.xf_ld >= (1ll << 29)) return hipErrorNotSupported;
-      return launch_gemv8_pro<whk::PRO_LN, 1>(a, stream);
+    case whk::PRO_PLAIN: return a.x_ld % 8 == 0 && (int64_t)a.R * a.x_ld < (1ll << 30);
+    case whk::PRO_LN: return a.ln_folded && a.xf_ld % 4 == 0 && (int64_t)a.R * a.xf_ld < (1ll << 29);
     case whk::PRO_COMBINE:
-      if (a.K != a.H * 64 || a.H > 20 || (int64_t)a.R * a.H * a.splits * 64 >= (1ll << 29)) return hipErrorNotSupported;
-      if (a.splits == 2) return launch_gemv8_pro<whk::PRO_COMBINE, 2>(a, stream);
-      if (a.splits == 3) return launch_gemv8_pro<whk::PRO_COMBINE, 3>(a, stream);
-      if (a.splits == 4) return launch_gemv8_pro<whk::PRO_COMBINE, 4>(a, stream);
-      return hipErrorNotSupported;
+      return a.K == a.H * 64 && a.H <= 20 && a.splits >= 2 && a.splits <= 4 && (int64_t)a.R * a.H * a.splits * 64 < (1ll << 29);
   }
-  return hipErrorNotSupported;
+  return false;
 }
 
+hipError_t launch_gemv8(const whk::GemvArgs& a, hipStream_t stream) {      // only where gemv8_applies
+  if (a.pro == whk::PRO_PLAIN) return launch_gemv8_pro<whk::PRO_PLAIN, 1>(a, stream);
+  if (a.pro == whk::PRO_LN) return launch_gemv8_pro<whk::PRO_LN, 1>(a, stream);
+  if (a.pro == whk::PRO_COMBINE && a.splits == 2) return launch_gemv8_pro<whk::PRO_COMBINE, 2>(a, stream);
+  if (a.pro == whk::PRO_COMBINE && a.splits == 3) return launch_gemv8_pro<whk::PRO_COMBINE, 3>(a, stream);
+  if (a.pro == whk::PRO_COMBINE && a.splits == 4) return launch_gemv8_pro<whk::PRO_COMBINE, 4>(a, stream);
+  return hipErrorInvalidValue;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
-// 17..48 rows (beam search: 8 clips x 5 beams = 40) behind a LayerNorm: ALL rows in one workgroup.
+// 25..48 rows (beam search: 8 clips x 5 beams = 40) behind a LayerNorm: ALL rows in one workgroup.
 // The 16-row tiles above put three row blocks on grid.y, so every 16 output features are handled by three workgroups
 // that each repeat a LayerNorm prologue and re-read the weights: 960 workgroups for FC1, 3.75 rounds per CU,
 // 14.9 us.  Here a 16-wave workgroup normalises all 48 rows once (3 per wave, in registers, fp16 into a bank-swizzled
@@ -1371,14 +1349,14 @@ __global__ __launch_bounds__(1024) void gemv_rows48_kernel(whk::GemvArgs a) {
   if (a.bump2 && blockIdx.x == 0 && tid == 0) atomicAdd(a.bump2, 1);
 }
 
-// applies to: fp16, LayerNorm prologue with folded affine part, 17..48 rows, K a multiple of 256 up to 1280,
-// store / GELU / QKV epilogues
+// applies to: fp16, LayerNorm prologue with folded affine part, 25..48 rows (up to WH_GEMV8_MAX_ROWS = 24 gemv8_kernel's row
+// tiles keep the job: pick_family), K a multiple of 256 up to 1280, store / GELU / QKV epilogues
 bool rows48_applies(const whk::GemvArgs& a) {
-  const bool off = WH_DEV_FLAG("WH_NO_ROWS48");   // developer A/B switch
   // measured at 40 rows, large-v3 (rocprof, real beam step): FC1 14.9 -> 11.4 us, QKV 11.7 -> 11.4 us; the D x D
   // cross-attention query got slower (7.9 -> 8.6 us: 80 workgroups each normalising all 48 rows), so N >= 2048 only
-  return !off && a.R > 16 && a.R <= 48 && a.pro == whk::PRO_LN && a.ln_folded && a.K % 256 == 0 && a.K <= 1280 &&
-         a.N >= 2048 && a.variant <= 0 && (a.epi == whk::EPI_STORE || a.epi == whk::EPI_GELU || a.epi == whk::EPI_QKV);
+  return !WH_DEV_FLAG("WH_NO_ROWS48") && a.R > WH_GEMV8_MAX_ROWS && a.R <= 48 && a.pro == whk::PRO_LN && a.ln_folded &&
+         a.K % 256 == 0 && a.K <= 1280 && a.N >= 2048 && a.variant <= 0 &&
+         (a.epi == whk::EPI_STORE || a.epi == whk::EPI_GELU || a.epi == whk::EPI_QKV);      // WH_NO_ROWS48: developer A/B switch
 }
 
 hipError_t launch_rows48(const whk::GemvArgs& a, hipStream_t stream) {
@@ -1389,7 +1367,6 @@ hipError_t launch_rows48(const whk::GemvArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL((gemv_rows48_kernel<2>), dim3((a.N + 31) / 32), dim3(1024), lds, stream, a);   // 32 features per workgroup
   return hipGetLastError();
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------
 // The tied logits projection (V x D, 133 MB at large-v3) for 17..48 rows.  The 16-row tiles put 3 row blocks on
@@ -1509,9 +1486,8 @@ __global__ __launch_bounds__(1024) void gemv_rows48_stream_kernel(whk::GemvArgs 
 
 // fp16, LayerNorm prologue, fp32 output without bias, 17..48 rows, K a multiple of 256 up to 1280, a long N
 bool rows48_stream_applies(const whk::GemvArgs& a) {
-  const bool off = WH_DEV_FLAG("WH_NO_ROWS48");   // developer A/B switch
-  return !off && a.R > 16 && a.R <= 48 && a.pro == whk::PRO_LN && a.epi == whk::EPI_F32 && !a.bias && a.K % 256 == 0 &&
-         a.K <= 1280 && a.N >= 16384 && a.variant <= 0;
+  return !WH_DEV_FLAG("WH_NO_ROWS48") && a.R > 16 && a.R <= 48 && a.pro == whk::PRO_LN && a.epi == whk::EPI_F32 && !a.bias &&
+         a.K % 256 == 0 && a.K <= 1280 && a.N >= 16384 && a.variant <= 0;
 }
 
 hipError_t launch_rows48_stream(const whk::GemvArgs& a, hipStream_t stream) {
@@ -1525,7 +1501,6 @@ hipError_t launch_rows48_stream(const whk::GemvArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(gemv_rows48_stream_kernel, dim3(wgs), dim3(1024), lds, stream, a);
   return hipGetLastError();
 }
-
 
 // The merge of PRO_COMBINE as its own launch, for 17+ rows: fused into the projection every 16-row workgroup merges
 // its rows x 20 heads x S splits again (480 workgroups, 59 MB of L2 reads at 40 rows: 11.3 us against 4.9 us for the
@@ -1568,6 +1543,41 @@ __global__ __launch_bounds__(256) void merge_partials_kernel(const T* __restrict
   Pack4<T>::store(out + (o_frag ? frag_elem(r, h * 64 + d4 * 4, H * 64) : (int64_t)r * o_ld + h * 64 + d4 * 4), num[0], num[1], num[2], num[3]);
 }
 
+// Which kernel family a projection runs on is decided here and nowhere else ("which kernel a projection runs on"):
+// pick_family reads its arguments and the developer switches and launches nothing; the first rule that holds wins.
+enum class Family { refuse, gemv8, rows48, rows48_stream, rows16_mf, rt4, rt8 };
+
+Family pick_family(const whk::GemvArgs& a, int dtype) {
+  if (a.R <= 0) return Family::refuse;
+  // only gemv8_kernel knows the fragment order (kernels.h): a caller that asks for it where that kernel does not run must hear
+  // about it (api.cpp::step_plan asks gemv8_will_run first) — never row-major arithmetic on fragment-order bytes
+  if (a.x_frag || a.y_frag) return dtype == 1 && a.R <= WH_GEMV8_MAX_ROWS && gemv8_applies(a) ? Family::gemv8 : Family::refuse;
+  // fp32 (strict-parity mode): x rows are twice as wide in LDS, and the 4-wave staging moves at most 24 units per
+  // thread per row (K <= 3072 at 8 rows, K <= 6144 at 4 rows)
+  if (dtype != 1) return a.R <= 4 || a.K > 3072 ? Family::rt4 : Family::rt8;
+  // the decode step (and the few-row prefill, and beam-search rows): MFMA diagonal form
+  // More rows (beam search: 8 clips x 5 beams = 40): every workgroup reads ALL x rows, so beyond 8 rows the x
+  // fragments (40 rows x K) outweigh its share of the weights; measured at 40 rows, large-v3 (profiles/r02_beam_*):
+  // the 24 / 48-row forms of gemv8 take 6.5 / 8.6 / 14.3 / 11.4 / 14.9 / 18.4 us (out, cq, cout, qkv, fc1, fc2) against
+  // 4.8 / 7.9 / 11.2 / 14.9 / 11.7 / 11.3 us for the 16-row LDS-staged MFMA tiles (`rows16` below) — those keep the job wherever
+  // they apply, behind the 48-row forms; gemv8's row blocks serve the remaining shapes (25..96 rows outside the 16-row limits).
+  if (rows48_applies(a)) return Family::rows48;
+  if (rows48_stream_applies(a)) return Family::rows48_stream;
+  // Round 5: 9 - 24 rows run on gemv8_kernel with TWO / THREE row tiles per weight fragment (the weights are streamed once,
+  // every weight wave holds that many sets of x fragments) instead of the 16-row LDS-staged tiles / the 48-row LayerNorm
+  // kernels: the whole step of large-v3 at 16 rows 2680 -> 2073 us, 12 rows 2472 -> 1855, 2 x 5 beam rows 2276 -> 1646,
+  // 3 x 5 2355 -> 1740, 4 x 5 2228 -> 1949, 24 rows 2862 -> 2609.  Beyond 24 rows it loses: 4 / 5 / 6 tiles at 32 / 40 rows
+  // 3526 / 3030 vs 3207 / 2571 us (every weight wave fetches all tiles' x fragments itself, the LayerNorm waves take 5 rows
+  // each), so 25 - 48 rows keep the LDS-staged forms (profiles/r05_rows24.txt).  WH_GEMV8_MAX_ROWS is the knob of that A/B;
+  // what gemv8 does not cover of 9 - 24 rows falls to the 16-row tiles after it.
+  // rows16: fp16, beam-search row counts (9+) — row tiles of 16 through the matrix cores while x (16 rows) fits in LDS
+  const bool rows16 = a.R > 8 && a.variant <= 0 && a.K % 128 == 0 && a.K <= 5120 && (a.K / 32 <= 40 || a.pro == whk::PRO_PLAIN);
+  if ((a.R <= WH_GEMV8_MAX_ROWS || !rows16) && gemv8_applies(a)) return Family::gemv8;
+  if (a.R <= 4) return Family::rt4;
+  if (rows16) return Family::rows16_mf;
+  return Family::rt8;                                 // 5..8 rows, or long K: row tiles of 8 on grid.y
+}
+
 }  // namespace
 
 namespace whk {
@@ -1575,52 +1585,35 @@ namespace whk {
 thread_local const char* g_form = "";
 
 hipError_t launch_gemv(const GemvArgs& a, int dtype, hipStream_t stream) {
-  if (a.R <= 0) return hipErrorInvalidValue;
-  if (a.x_frag || a.y_frag) {
-    // only gemv8_kernel knows the fragment order (kernels.h): a caller that asks for it where that kernel does not run must hear
-    // about it (api.cpp::step_plan asks gemv8_will_run first) — never row-major arithmetic on fragment-order bytes
-    if (dtype != 1 || a.R > WH_GEMV8_MAX_ROWS) return hipErrorInvalidValue;
-    const hipError_t e = launch_gemv8(a, stream);
-    return e == hipErrorNotSupported ? hipErrorInvalidValue : e;
-  }
+  const Family f = pick_family(a, dtype);
   if (dtype == 1) {
-    // the decode step (and the few-row prefill, and beam-search rows): MFMA diagonal form
-    // More rows (beam search: 8 clips x 5 beams = 40): every workgroup reads ALL x rows, so beyond 8 rows the x
-    // fragments (40 rows x K) outweigh its share of the weights; measured at 40 rows, large-v3 (profiles/r02_beam_*):
-    // the 24 / 48-row forms of gemv8 take 6.5 / 8.6 / 14.3 / 11.4 / 14.9 / 18.4 us (out, cq, cout, qkv, fc1, fc2) against
-    // 4.8 / 7.9 / 11.2 / 14.9 / 11.7 / 11.3 us for the 16-row LDS-staged MFMA tiles below — those keep the job wherever
-    // they apply; gemv8's row blocks serve the remaining shapes (row counts 9..96 outside the 16-row form's limits).
-    if (a.R > WH_GEMV8_MAX_ROWS || a.epi == whk::EPI_F32) {
-      if (rows48_applies(a)) return launch_rows48(a, stream);
-      if (rows48_stream_applies(a)) return launch_rows48_stream(a, stream);
+    switch (f) {
+      case Family::gemv8: return launch_gemv8(a, stream);
+      case Family::rows48: return launch_rows48(a, stream);
+      case Family::rows48_stream: return launch_rows48_stream(a, stream);
+      case Family::rt4: return launch_rt<half_t, 4>(a, stream);
+      case Family::rows16_mf: return launch_rows16_mf<half_t>(a, stream);
+      case Family::rt8: return launch_rt<half_t, 8>(a, stream);
+      case Family::refuse: break;
     }
-    bool rows16 = a.R > 8 && a.variant <= 0 && a.K % 128 == 0 && a.K <= 5120 && (a.K / 32 <= 40 || a.pro == whk::PRO_PLAIN);
-    // Round 5: 9 - 24 rows run on gemv8_kernel with TWO / THREE row tiles per weight fragment (the weights are streamed once,
-    // every weight wave holds that many sets of x fragments) instead of the 16-row LDS-staged tiles / the 48-row LayerNorm
-    // kernels: the whole step of large-v3 at 16 rows 2680 -> 2073 us, 12 rows 2472 -> 1855, 2 x 5 beam rows 2276 -> 1646,
-    // 3 x 5 2355 -> 1740, 4 x 5 2228 -> 1949, 24 rows 2862 -> 2609.  Beyond 24 rows it loses: 4 / 5 / 6 tiles at 32 / 40 rows
-    // 3526 / 3030 vs 3207 / 2571 us (every weight wave fetches all tiles' x fragments itself, the LayerNorm waves take 5 rows
-    // each), so 25 - 48 rows keep the LDS-staged forms (profiles/r05_rows24.txt).  WH_GEMV8_MAX_ROWS is the knob of that A/B.
-    if (a.R <= WH_GEMV8_MAX_ROWS) rows16 = false;
-    if (a.R <= 96 && !rows16) {
-      const hipError_t e = launch_gemv8(a, stream);
-      if (e != hipErrorNotSupported) return e;
-    }
-    if (a.R <= 4) return launch_rt<half_t, 4>(a, stream);
-    // beam-search row counts: row tiles of 16 through the matrix cores while x (16 rows) fits in LDS
-    if (a.R > 8 && a.variant <= 0 && a.K % 128 == 0 && a.K <= 5120 && (a.K / 32 <= 40 || a.pro == whk::PRO_PLAIN))
-      return launch_rows16_mf<half_t>(a, stream);
-    return launch_rt<half_t, 8>(a, stream);           // R <= 8, or long K: row tiles of 8 on grid.y
+  } else if (f == Family::rt4 || f == Family::rt8) {          // fp32: the v_dot2 row tiles only
+    return f == Family::rt4 ? launch_rt<float, 4>(a, stream) : launch_rt<float, 8>(a, stream);
   }
-  // fp32 (strict-parity mode): x rows are twice as wide in LDS, and the 4-wave staging moves at most 24 units per
-  // thread per row (K <= 3072 at 8 rows, K <= 6144 at 4 rows)
-  if (a.R <= 4 || (size_t)a.K * 8 * sizeof(float) > 128 * 1024 || a.K > 3072) return launch_rt<float, 4>(a, stream);
-  return launch_rt<float, 8>(a, stream);
+  return hipErrorInvalidValue;
 }
 
-// true when launch_gemv hands (R rows, fp16) x (N, K, pro) to gemv8_kernel — the only kernel that reads x_frag and writes y_frag
+// pick_family's answer by name ("" = refused), for the kernel test library
+const char* gemv_family(const GemvArgs& a, int dtype) {
+  static const char* const names[] = {"", "gemv8", "rows48", "rows48_stream", "rows16_mf", "rt4", "rt8"};
+  return names[(int)pick_family(a, dtype)];
+}
+
+// the canonical launch of kernels.h as a fragment-order request: launch_gemv honours it exactly where gemv8_kernel runs
 bool gemv8_will_run(int R, int N, int K, int pro) {
-  return gemv8_enabled() && R >= 1 && R <= WH_GEMV8_MAX_ROWS && gemv8_covers(N, K, pro);
+  GemvArgs a = {};
+  a.pro = pro; a.R = R; a.N = N; a.K = K; a.x_ld = a.xf_ld = K; a.ln_folded = 1; a.splits = 2; a.H = K / 64;
+  a.epi = EPI_STORE; a.y_frag = 1;
+  return pick_family(a, 1) == Family::gemv8;
 }
 
 hipError_t launch_merge_partials(const void* part_o, const float* part_ml, int splits, int R, int H, void* out,

@@ -242,7 +242,7 @@ struct GemvArgs {
   const int* lag;                                 // EPI_QKV: per-row position lag (ragged prompts); may be null
   int* bump; int bump_by;                         // optional: *bump += bump_by once per launch (position counter)
   int* bump2;                                     // optional: *bump2 += 1 once per launch (the step tick of xattn.hip)
-  int variant;                                    // 0 = shape heuristic; > 0 forces a kernel shape (tools/probe_decode)
+  int variant;                                    // 0 = shape heuristic; > 0 forces a kernel shape (tools/probe_decode); < 0 = heuristic without gemv8
   WH_PROBE_FIELD
 };
 hipError_t launch_gemv(const GemvArgs& a, int dtype, hipStream_t stream);
@@ -261,7 +261,14 @@ hipError_t launch_gemv(const GemvArgs& a, int dtype, hipStream_t stream);
 static inline int64_t frag_index(int r, int k, int K) {
   return ((((int64_t)(r >> 3) * (K >> 6) + (k >> 6)) * 64 + 16 * ((k & 31) >> 3) + 8 * ((k >> 5) & 1) + (r & 7)) << 3) + (k & 7);
 }
-bool gemv8_will_run(int R, int N, int K, int pro);      // launch_gemv(R rows of fp16) goes to gemv8_kernel for this shape
+// true when launch_gemv honours a fragment-order request for (R rows) x (N, K, pro), i.e. hands it to gemv8_kernel.  Asked about
+// the canonical launch of that shape: fp16, packed rows (x_ld = xf_ld = K), folded LayerNorm (PRO_LN: the caller checks
+// WH_WEIGHTS_DEC_LN_FOLDED itself), EPI_STORE, and for PRO_COMBINE splits = 2 and H = K / 64 heads.  A launch that differs
+// from it (padded rows, EPI_F32 with N > 16384, other split counts) may still be refused: gemv.hip, gemv8_applies.
+bool gemv8_will_run(int R, int N, int K, int pro);
+// the kernel family launch_gemv picks for `a`, decided without launching: "gemv8", "rows48", "rows48_stream", "rows16_mf", "rt4",
+// "rt8", or "" where it refuses (gemv.hip: pick_family; read by the kernel test library)
+const char* gemv_family(const GemvArgs& a, int dtype);
 // PRO_COMBINE's merge of the decode-attention partials as a launch of its own ([rows][H*64] in the element type)
 hipError_t launch_merge_partials(const void* part_o, const float* part_ml, int splits, int R, int H, void* out,
                                  int64_t o_ld, int dtype, hipStream_t stream, int o_frag = 0);

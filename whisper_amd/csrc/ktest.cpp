@@ -15,6 +15,16 @@ const char* wht_last_form() { return g_form; }
 void wht_clear_form() { g_form = ""; }
 int wht_attn_decode_capacity(int dtype) { return attn_decode_capacity(dtype); }
 int wht_gemv8_will_run(int R, int N, int K, int pro) { return gemv8_will_run(R, N, K, pro) ? 1 : 0; }
+// the family launch_gemv would pick ("" = refused); launches nothing.  ld is x_ld (PRO_PLAIN) or xf_ld (PRO_LN)
+const char* wht_gemv_family(int dtype, int pro, int epi, int R, int N, int K, int64_t ld, int ln_folded, int has_bias, int splits,
+                            int H, int x_frag, int y_frag) {
+  static const float some_bias = 0.f;
+  GemvArgs a;
+  memset(&a, 0, sizeof a);
+  a.pro = pro; a.epi = epi; a.R = R; a.N = N; a.K = K; a.x_ld = a.xf_ld = ld; a.ln_folded = ln_folded;
+  a.bias = has_bias ? &some_bias : nullptr; a.splits = splits; a.H = H; a.x_frag = x_frag; a.y_frag = y_frag;
+  return gemv_family(a, dtype);
+}
 
 int wht_gemv(int dtype, int pro, const void* x, int64_t x_ld, const float* xf, int64_t xf_ld, const float* ln_w,
              const float* ln_b, int ln_folded, const void* part_o, const float* part_ml, int splits, int H, const void* W,
