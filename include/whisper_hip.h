@@ -42,8 +42,10 @@ enum {
                           * from the prompt (wh_task_info(t, 4) counts these re-runs).  After host-driven wh_task_step
                           * calls ask wh_task_info(t, 1); create the task with WH_TASK_TWO_LAUNCH_SELF |
                           * WH_TASK_TWO_LAUNCH_CROSS to stay off the fused kernels from the start. */
-  WH_RUNNING = 7         /* not an error: wh_task_poll — the loop begun with wh_task_greedy_begin / wh_task_beam_begin has not
+  WH_RUNNING = 7,        /* not an error: wh_task_poll — the loop begun with wh_task_greedy_begin / wh_task_beam_begin has not
                           * ended yet; call again */
+  WH_ERR_STREAM = 8      /* wh_flac_decode_device: the FLAC stream fails its checks (a frame's CRC-16, a gap in the chain of
+                          * frames, fewer samples than STREAMINFO declares); callers hand the file to the host decoder */
 };
 
 /* element type of weights / activations / KV caches. Accumulation is always fp32. */
@@ -167,6 +169,32 @@ enum {
  * back to a host resampler.  n_frames == 0 succeeds and writes nothing.  Stream-ordered: the call does not wait. */
 int wh_resample(const void *pcm, int sample_format, int bits, int channels, int64_t n_frames, const double *taps,
                 int up, int down, int half_len, float *out, int64_t n_out, void *stream);
+
+/* ---- FLAC decoding on the device (csrc/flac.hip) ------------------------------------------- */
+/* A whole FLAC file in device memory -> interleaved int32 PCM [n_frames][channels] in device memory, the samples
+ * wh_flac_decode (whisper_audio.h) produces, bit for bit.  The caller has parsed the metadata on the host (ID3v2 skip,
+ * STREAMINFO) and passes: first_frame = the offset of the first frame, channels, bits_per_sample, max_block (STREAMINFO's
+ * maximum block size) and total_samples (per channel).  Frames are independent, so the device tests every byte offset as a
+ * frame start (header codes consistent with the stream, CRC-8), decodes every candidate in a lane of its own into
+ * `pcm` — the staging buffer, [staging_frames][channels], staging_frames >= total_samples plus room for false candidates,
+ * each of which claims its header's block size (<= 65535) — and records where each ended and whether its CRC-16 held.
+ * The host then walks the candidates once, from first_frame: a frame belongs to the stream when it starts where the
+ * previous one ended.  THAT DOWNLOAD IS THE CALL'S ONLY WAIT for a stream without false candidates; with them, the chained
+ * frames are moved to the front of `pcm` through the scratch, and the call waits once more for that.
+ * Verified: every frame's CRC-8 and CRC-16, the unbroken chain, the sample count against total_samples (fewer: WH_ERR_STREAM,
+ * more: trimmed), at most 128 trailing bytes.  NOT verified: the STREAMINFO MD5 signature, which is serial over all PCM.
+ * *n_frames_out = samples per channel at the front of `pcm`.  stats (optional, host int32[4]): candidates, chained frames,
+ * 1 if frames had to be moved, 0.
+ * WH_ERR_ARG: null pointers, channels outside 1 - 8, first_frame >= size, size > 2^40, max_block outside 16 - 65535,
+ * staging_frames < total_samples or > 2^40, max_candidates < 1 or > 2^24; WH_ERR_LIMIT (before any device work): what the
+ * route does not take — bits_per_sample outside 4 - 24, total_samples == 0; WH_ERR_WORKSPACE: scratch_bytes below
+ * wh_flac_device_scratch_bytes, or more candidates than max_candidates; WH_ERR_STREAM: the stream fails its checks (this
+ * covers what the narrow route refuses inside a frame: reserved subframe types, a negative LPC shift, a value outside
+ * int32).  After any status but WH_OK the contents of `pcm` are unspecified and the caller takes the host decoder. */
+size_t wh_flac_device_scratch_bytes(size_t size, int channels, int64_t staging_frames, int max_candidates);
+int wh_flac_decode_device(const uint8_t *file, size_t size, size_t first_frame, int channels, int bits_per_sample,
+                          int max_block, int64_t total_samples, int32_t *pcm, int64_t staging_frames, int max_candidates,
+                          int64_t *n_frames_out, int32_t *stats, void *scratch, size_t scratch_bytes, void *stream);
 
 /* ---- model handle -------------------------------------------------------------------------- */
 /* Stands in for Whisper.__init__ + load_state_dict (whisper/__init__.py:154-156): the caller has

@@ -34,7 +34,7 @@ from typing import TYPE_CHECKING, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from .audio import FRAMES_PER_SECOND, N_FRAMES, N_SAMPLES, TOKENS_PER_SECOND, load_audio, log_mel_spectrogram, pad_or_trim
+from .audio import FRAMES_PER_SECOND, N_FRAMES, N_SAMPLES, TOKENS_PER_SECOND, ingest_options, load_audio, log_mel_spectrogram, pad_or_trim
 from .timing import WordTiming, find_alignment_open_batch, merge_punctuations
 from .tokenizer import LANGUAGES, Tokenizer, get_tokenizer
 
@@ -220,6 +220,7 @@ def align_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray, torch.
     dtype = torch.float16 if fp16 and model.device != torch.device("cpu") else torch.float32
     guard_frames = int(round(guard_s * TOKENS_PER_SECOND)) * FRAMES_PER_TOKEN
     results: List[Optional[dict]] = [None] * len(audios)
+    ingest = ingest_options(device_ingest)       # False / True / "decode", as in transcribe
     waiting = list(range(len(audios)))
     live: List[tuple] = []                       # (file index, state, tokenizer, language)
 
@@ -227,8 +228,8 @@ def align_batch(model: "Whisper", audios: Sequence[Union[str, np.ndarray, torch.
         while waiting and len(live) < batch_size:
             i = waiting.pop(0)
             audio = audios[i]
-            if device_ingest and isinstance(audio, str):
-                audio = load_audio(audio, device=model.device)
+            if ingest is not None and isinstance(audio, str):
+                audio = load_audio(audio, device=model.device, **ingest)
             mel = log_mel_spectrogram(audio, model.dims.n_mels, padding=N_SAMPLES, device=model.device)
             lang = language
             if lang is None:

@@ -200,12 +200,64 @@ def _sniff(file: str) -> Optional[str]:
 MAX_DEVICE_CHANNELS = 8             # wh_resample: 1 - 8 channels
 
 
-def _ingest_host(file: str, sr: int):
+def parse_flac_info(data) -> Optional["hip.FlacInfo"]:
+    """The metadata of a FLAC file held in memory, as csrc/flac_decode.c reads it: an ID3v2 tag is skipped, STREAMINFO gives
+    rate, channels, sample size, sample count and block sizes, the first frame follows the last metadata block.  None for
+    anything the host decoder would refuse at this point (it is the one to say why)."""
+    n, pos = len(data), 0
+    if n >= 10 and bytes(data[:3]) == b"ID3":
+        pos = 10 + ((data[6] & 127) << 21 | (data[7] & 127) << 14 | (data[8] & 127) << 7 | (data[9] & 127))
+    if pos + 4 > n or bytes(data[pos: pos + 4]) != b"fLaC":
+        return None
+    pos += 4
+    info = None
+    while True:
+        if pos + 4 > n:
+            return None
+        last, kind = data[pos] >> 7, data[pos] & 127
+        size = data[pos + 1] << 16 | data[pos + 2] << 8 | data[pos + 3]
+        pos += 4
+        if pos + size > n:
+            return None
+        if kind == 0:
+            if size < 34:
+                return None
+            q = data[pos: pos + 34]
+            info = dict(min_block=q[0] << 8 | q[1], max_block=q[2] << 8 | q[3], sample_rate=q[10] << 12 | q[11] << 4 | q[12] >> 4,
+                        channels=((q[12] >> 1) & 7) + 1, bits_per_sample=((q[12] & 1) << 4 | q[13] >> 4) + 1,
+                        total_samples=(q[13] & 15) << 32 | q[14] << 24 | q[15] << 16 | q[16] << 8 | q[17])
+        pos += size
+        if last:
+            break
+    if info is None or info["sample_rate"] == 0 or info["max_block"] < 16 or not 4 <= info["bits_per_sample"] <= 32:
+        return None
+    return hip.FlacInfo(first_frame=pos, **info)
+
+
+class _FlacFile:
+    """a FLAC file read but not decoded: what `_ingest_host(..., decode_on_device=True)` hands `_ingest_device`"""
+    __slots__ = ("data", "info")
+
+    def __init__(self, data, info):
+        self.data, self.info = data, info
+
+
+def _ingest_host(file: str, sr: int, decode_on_device: bool = False):
     """Host half of the device-side ingest (thread-safe; the FLAC decoder releases the GIL): the stored PCM of a WAV / FLAC
     file as (pcm, rate, bits).  Everything the native route does not take — another container (an ID3-tagged MP3 included), a
     WAV / FLAC the native readers refuse (an encoding they do not know, a stream that fails its checks), more than 8
-    channels — goes the way `load_audio(file, sr)` goes, ffmpeg first, and comes back as samples."""
+    channels — goes the way `load_audio(file, sr)` goes, ffmpeg first, and comes back as samples.
+    `decode_on_device`: a FLAC file the device decoder takes (4 - 24 bits per sample, a sample count in STREAMINFO, a first
+    frame inside the file) is only read here, and comes back as a `_FlacFile`."""
     kind, parsed = _sniff(file), None
+    if decode_on_device and kind == "flac":
+        with open(file, "rb") as f:
+            data = bytearray(os.fstat(f.fileno()).st_size)
+            data = data[: f.readinto(data)]
+        info = parse_flac_info(data)
+        if (info is not None and info.bits_per_sample <= 24 and info.total_samples > 0 and info.channels <= MAX_DEVICE_CHANNELS
+                and info.first_frame < len(data)):
+            return _FlacFile(data, info)
     if kind == "wav":
         parsed = _parse_wav(file)
     elif kind == "flac":
@@ -220,7 +272,19 @@ def _ingest_host(file: str, sr: int):
 
 def _ingest_device(staged, file: str, sr: int, device: torch.device) -> torch.Tensor:
     """Device half: upload the PCM in its stored width, then down-mix + resample + quantise in one kernel (hip.resample) on
-    the calling thread's current stream; samples that came from the host route are uploaded as they are."""
+    the calling thread's current stream; samples that came from the host route are uploaded as they are.  A `_FlacFile` is
+    uploaded as the bytes it is and decoded there (hip.flac_decode_device); its int32 PCM goes into the same hip.resample.
+    Whatever the device decoder refuses or rejects is handed to `_ingest_host`: the host decoder decides, or raises."""
+    if isinstance(staged, _FlacFile):
+        info = staged.info
+        rc, pcm, _ = hip.flac_decode_device(torch.frombuffer(staged.data, dtype=torch.uint8).to(device), info)
+        if rc == 0:
+            try:
+                return hip.resample(pcm, info.sample_rate, sr, info.bits_per_sample)
+            except hip.HipLimitError:
+                staged = load_audio(file, sr)
+        else:
+            staged = _ingest_host(file, sr)
     if isinstance(staged, tuple):
         pcm, rate, bits = staged
         try:
@@ -231,7 +295,19 @@ def _ingest_device(staged, file: str, sr: int, device: torch.device) -> torch.Te
     return torch.from_numpy(staged).to(device)
 
 
-def load_audio(file: str, sr: int = SAMPLE_RATE, device: Optional[Union[str, torch.device]] = None):
+def ingest_options(device_ingest) -> Optional[dict]:
+    """`device_ingest` of the entry points -> the keywords `load_audio(path, device=model.device, ...)` gets beyond `device`:
+    None for False (host ingest), {} for True, {"decode_on_device": True} for "decode" (FLAC files are decoded on the GPU
+    as well)."""
+    if isinstance(device_ingest, str):
+        if device_ingest != "decode":
+            raise ValueError(f'device_ingest must be False, True or "decode" (got {device_ingest!r})')
+        return {"decode_on_device": True}
+    return {} if device_ingest else None
+
+
+def load_audio(file: str, sr: int = SAMPLE_RATE, device: Optional[Union[str, torch.device]] = None,
+               decode_on_device: bool = False):
     """Decode `file` to mono float32 at `sr` Hz.  Same contract as the reference (audio.py:25-62): ffmpeg does
     the decoding / down-mixing / resampling; a RuntimeError is raised when it fails.  When the ffmpeg binary
     does not exist, RIFF/WAVE files are read natively and FLAC files through the native decoder of
@@ -245,10 +321,18 @@ def load_audio(file: str, sr: int = SAMPLE_RATE, device: Optional[Union[str, tor
     resampler — the host route where ffmpeg is installed — no bound is claimed or has been measured: it is a different
     filter, as it always was for the native route.  Other containers, WAV / FLAC files the native readers refuse, files with
     more than 8 channels and rate pairs whose filter the kernel does not take go the host route (ffmpeg first) and are
-    uploaded.  hip.HipError without a GPU."""
+    uploaded.  hip.HipError without a GPU.
+
+    `decode_on_device` (with `device`; opt-in): a FLAC file is not decoded on the host either.  Its bytes are uploaded and
+    csrc/flac.hip decodes it there, one lane per frame, to the int32 PCM the host decoder produces, bit for bit — so the
+    result equals the one without the flag.  The one difference: this route verifies every frame's CRC-8 and CRC-16, the
+    unbroken chain of frames and the sample count, but not the STREAMINFO MD5 signature.  What it does not take (32-bit
+    FLAC, a stream without a sample count) or rejects goes to the host decoder exactly as without the flag."""
     if device is not None:
         device = torch.device(device)
         hip.require_gpu(device)
+        if decode_on_device:
+            return _ingest_device(_ingest_host(file, sr, True), file, sr, device)
         return _ingest_device(_ingest_host(file, sr), file, sr, device)
     cmd = ["ffmpeg", "-nostdin", "-threads", "0", "-i", file, "-f", "s16le", "-ac", "1",
            "-acodec", "pcm_s16le", "-ar", str(sr), "-"]

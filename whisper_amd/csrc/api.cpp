@@ -3,6 +3,7 @@
 // Host code only: all device work is in the .hip files behind kernels.h.
 #include "../../include/whisper_hip.h"
 #include "kernels.h"
+#include "flac_core.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -38,6 +39,7 @@ extern "C" const char* wh_status_string(int s) {
     case WH_ERR_LIMIT: return "compiled-in limit exceeded";
     case WH_ERR_HANDOFF: return "in-kernel hand-off timed out (results invalid)";
     case WH_RUNNING: return "loop still running (call wh_task_poll again)";
+    case WH_ERR_STREAM: return "the FLAC stream fails its checks";
     default: return "unknown status";
   }
 }
@@ -1900,5 +1902,83 @@ extern "C" int wh_resample(const void* pcm, int sample_format, int bits, int cha
   if (n_frames == 0) return WH_OK;
   HIPCHK(launch_resample(pcm, sample_format, bits, channels, n_frames, taps, up, down, half_len, out, n_out,
                          (hipStream_t)stream));
+  return WH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// FLAC decoding on the device (flac.hip): scan -> decode -> [download, chain on the host] -> compact
+// ------------------------------------------------------------------------------------------------
+static bool flac_args_ok(size_t size, int channels, int64_t staging_frames, int max_candidates) {
+  return size > 0 && size <= ((size_t)1 << 40) && channels >= 1 && channels <= FLAC_MAX_CHANNELS && staging_frames >= 1 &&
+         staging_frames <= ((int64_t)1 << 40) && max_candidates >= 1 && max_candidates <= (1 << 24);
+}
+
+extern "C" size_t wh_flac_device_scratch_bytes(size_t size, int channels, int64_t staging_frames, int max_candidates) {
+  if (!flac_args_ok(size, channels, staging_frames, max_candidates)) return 0;
+  return flac_scratch(nullptr, size, channels, staging_frames, max_candidates).total_bytes;
+}
+
+extern "C" int wh_flac_decode_device(const uint8_t* file, size_t size, size_t first_frame, int channels, int bits_per_sample,
+                                     int max_block, int64_t total_samples, int32_t* pcm, int64_t staging_frames,
+                                     int max_candidates, int64_t* n_frames_out, int32_t* stats, void* scratch,
+                                     size_t scratch_bytes, void* stream) {
+  if (!file || !pcm || !n_frames_out || !scratch) return WH_ERR_ARG;
+  if (!flac_args_ok(size, channels, staging_frames, max_candidates) || first_frame >= size || max_block < 16 ||
+      max_block > FLAC_MAX_BLOCK || total_samples < 0 || staging_frames < total_samples)
+    return WH_ERR_ARG;
+  if (bits_per_sample < 4 || bits_per_sample > 24 || total_samples == 0) return WH_ERR_LIMIT;
+  const FlacScratch s = flac_scratch(scratch, size, channels, staging_frames, max_candidates);
+  if (scratch_bytes < s.total_bytes) return WH_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  *n_frames_out = 0;
+  if (stats) memset(stats, 0, 4 * sizeof(int32_t));
+
+  HIPCHK(launch_flac_scan(file, size, first_frame, channels, bits_per_sample, max_block, s, max_candidates, st));
+  HIPCHK(launch_flac_decode(file, size, channels, bits_per_sample, s, max_candidates, pcm, staging_frames, st));
+  std::vector<uint8_t> host(s.record_bytes);
+  HIPCHK(hipMemcpyAsync(host.data(), scratch, s.record_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                                  // the call's one wait (see whisper_hip.h)
+
+  const FlacScratch h = flac_scratch(host.data(), size, channels, staging_frames, max_candidates);   // the same layout, host copy
+  const int n_cand = h.hdr[0];
+  if (stats) stats[0] = h.hdr[1];
+  if (h.hdr[1] > max_candidates || n_cand < 0 || n_cand > max_candidates) return WH_ERR_WORKSPACE;
+  std::vector<int32_t> accepted((size_t)n_cand + 1);
+  int n_acc = 0;
+  int64_t done = 0;
+  if (flac_chain(h.start, h.end, h.bs, h.rc, n_cand, first_frame, size, h.tail, (uint64_t)total_samples, accepted.data(), &n_acc,
+                 &done) != FLAC_OK)
+    return WH_ERR_STREAM;
+  if (stats) stats[1] = n_acc;
+  if (n_acc != n_cand) {
+    // false candidates left gaps: chained frame k goes from its provisional position to the sum of the chained blocks before it
+    std::vector<int64_t> prov((size_t)n_cand + 1), from, to;
+    std::vector<int32_t> len;
+    int64_t at = 0;
+    for (int j = 0; j < n_cand; ++j) { prov[j] = at; at += h.bs[j]; }
+    at = 0;
+    int64_t lo = -1, hi = 0;
+    for (int k = 0; k < n_acc; ++k) {
+      const int j = accepted[k];
+      if (prov[j] != at) {
+        if (lo < 0) lo = at;
+        from.push_back(prov[j] * channels); to.push_back(at * channels); len.push_back(h.bs[j] * channels);
+        hi = at + h.bs[j];
+      }
+      at += h.bs[j];
+    }
+    if (!from.empty()) {
+      const size_t n = from.size();
+      HIPCHK(hipMemcpyAsync(s.mv_from, from.data(), n * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(s.mv_to, to.data(), n * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(s.mv_len, len.data(), n * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(launch_flac_move(pcm, s.temp, s, (int)n, st));
+      HIPCHK(hipMemcpyAsync(pcm + lo * channels, s.temp + lo * channels, (size_t)(hi - lo) * channels * 4,
+                            hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));                              // the lists above are this call's own
+      if (stats) stats[2] = 1;
+    }
+  }
+  *n_frames_out = done > total_samples ? total_samples : done;
   return WH_OK;
 }

@@ -13,13 +13,23 @@
  *                       int* channels, int* sample_rate, int* bits_per_sample);   // 0 = ok, < 0 = error code
  *   void wh_flac_free(int32_t* samples);
  *   const char* wh_flac_error(int code);
+ *
+ * The per-frame logic (bit reader, CRCs, frame header, subframes, decorrelation) lives in flac_core.h, which csrc/flac.hip
+ * compiles a second time as device code.  wh_flac_decode_frames (include/whisper_flac_frames.h) is the serial twin of that
+ * GPU route: the same scan -> per-candidate decode -> chain -> compact algorithm, testable without a GPU.
  */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
-enum { FLAC_OK = 0, FLAC_E_MAGIC = -1, FLAC_E_TRUNC = -2, FLAC_E_HEADER = -3, FLAC_E_CRC = -4, FLAC_E_UNSUP = -5,
-       FLAC_E_MD5 = -6, FLAC_E_MEM = -7, FLAC_E_SYNC = -8 };
+#include "flac_core.h"
+#define FLAC_T int64_t
+#define FLAC_SUFFIX _w
+#include "flac_core.h"
+#define FLAC_T int32_t
+#define FLAC_SUFFIX _n
+#include "flac_core.h"
+#include "../../include/whisper_flac_frames.h"
 
 const char* wh_flac_error(int code) {
   switch (code) {
@@ -34,65 +44,6 @@ const char* wh_flac_error(int code) {
     case FLAC_E_SYNC: return "lost FLAC frame sync";
     default: return "unknown FLAC error";
   }
-}
-
-/* ---------------------------------------------------------------- bit reader (MSB first) */
-typedef struct { const uint8_t* p; size_t n, pos; uint64_t acc; int bits; int eof; } BR;
-
-static void br_init(BR* b, const uint8_t* p, size_t n, size_t pos) { b->p = p; b->n = n; b->pos = pos; b->acc = 0; b->bits = 0; b->eof = 0; }
-static void br_fill(BR* b) {
-  while (b->bits <= 56) {
-    uint64_t byte = 0;
-    if (b->pos < b->n) byte = b->p[b->pos];
-    else if (b->pos >= b->n + 8) { b->eof = 1; }
-    b->pos++;
-    b->acc |= byte << (56 - b->bits);
-    b->bits += 8;
-  }
-}
-static uint32_t br_u(BR* b, int n) {            /* n in 0..32 */
-  if (n == 0) return 0;
-  if (b->bits < n) br_fill(b);
-  uint32_t v = (uint32_t)(b->acc >> (64 - n));
-  b->acc <<= n; b->bits -= n;                      /* n <= 32 */
-  return v;
-}
-static int32_t br_s(BR* b, int n) {             /* signed, n in 1..32 */
-  uint32_t v = br_u(b, n);
-  if (n < 32 && (v >> (n - 1))) v |= ~0u << n;
-  return (int32_t)v;
-}
-static int64_t br_s64(BR* b, int n) {           /* signed up to 33 bits (side channel of 32-bit audio) */
-  if (n <= 32) return br_s(b, n);
-  int64_t hi = br_s(b, n - 32);
-  return (hi << 32) | br_u(b, 32);
-}
-static uint32_t br_unary(BR* b) {               /* number of 0 bits before the next 1 bit */
-  uint32_t q = 0;
-  for (;;) {
-    if (b->bits == 0) br_fill(b);
-    if (b->acc == 0) { q += b->bits; b->bits = 0; if (b->eof) return q; continue; }
-    int z = __builtin_clzll(b->acc);
-    if (z >= b->bits) { q += b->bits; b->acc = 0; b->bits = 0; continue; }
-    q += z;
-    b->acc = z == 63 ? 0 : b->acc << (z + 1);      /* a 64-bit shift would be undefined */
-    b->bits -= z + 1;
-    return q;
-  }
-}
-static size_t br_bytepos(const BR* b) { return b->pos - (size_t)(b->bits / 8); }   /* valid when byte aligned */
-static void br_align(BR* b) { int r = b->bits & 7; b->acc <<= r; b->bits -= r; }
-
-/* ---------------------------------------------------------------- CRCs */
-static uint8_t crc8(const uint8_t* p, size_t n) {
-  uint8_t c = 0;
-  for (size_t i = 0; i < n; ++i) { c ^= p[i]; for (int k = 0; k < 8; ++k) c = (uint8_t)((c & 0x80) ? (c << 1) ^ 0x07 : c << 1); }
-  return c;
-}
-static uint16_t crc16(const uint8_t* p, size_t n) {
-  uint16_t c = 0;
-  for (size_t i = 0; i < n; ++i) { c ^= (uint16_t)(p[i] << 8); for (int k = 0; k < 8; ++k) c = (uint16_t)((c & 0x8000) ? (c << 1) ^ 0x8005 : c << 1); }
-  return c;
 }
 
 /* ---------------------------------------------------------------- MD5 (RFC 1321) */
@@ -138,93 +89,10 @@ static void md5_final(MD5* m, uint8_t out[16]) {
   for (int i = 0; i < 4; ++i) for (int k = 0; k < 4; ++k) out[4*i+k] = (uint8_t)(m->h[i] >> (8 * k));
 }
 
-/* ---------------------------------------------------------------- subframes */
-static int read_residual(BR* b, int64_t* s, int blocksize, int order) {
-  int method = (int)br_u(b, 2);
-  if (method > 1) return FLAC_E_UNSUP;
-  int pbits = method == 0 ? 4 : 5, esc = method == 0 ? 15 : 31;
-  int porder = (int)br_u(b, 4);
-  int nparts = 1 << porder;
-  if ((blocksize >> porder) << porder != blocksize && porder > 0) return FLAC_E_HEADER;
-  int i = order;
-  for (int part = 0; part < nparts; ++part) {
-    int count = (blocksize >> porder) - (part == 0 ? order : 0);
-    if (count < 0) return FLAC_E_HEADER;
-    int k = (int)br_u(b, pbits);
-    if (k == esc) {
-      int nb = (int)br_u(b, 5);
-      for (int j = 0; j < count; ++j) s[i++] = nb ? br_s(b, nb) : 0;
-    } else {
-      for (int j = 0; j < count; ++j) {
-        uint32_t q = br_unary(b);
-        uint64_t u = ((uint64_t)q << k) | br_u(b, k);
-        s[i++] = (int64_t)(u >> 1) ^ -(int64_t)(u & 1);
-      }
-    }
-    if (b->eof) return FLAC_E_TRUNC;
-  }
-  return FLAC_OK;
-}
+/* ---------------------------------------------------------------- metadata */
+typedef struct { int sr, ch, bps, max_block; uint64_t total; uint8_t md5[16]; size_t first; } flac_info;
 
-static int read_subframe(BR* b, int64_t* s, int blocksize, int bps) {
-  if (br_u(b, 1)) return FLAC_E_HEADER;
-  int type = (int)br_u(b, 6);
-  int wasted = 0;
-  if (br_u(b, 1)) wasted = (int)br_unary(b) + 1;
-  bps -= wasted;
-  if (bps <= 0) return FLAC_E_HEADER;
-  if (type == 0) {
-    int64_t v = br_s64(b, bps);
-    for (int i = 0; i < blocksize; ++i) s[i] = v;
-  } else if (type == 1) {
-    for (int i = 0; i < blocksize; ++i) s[i] = br_s64(b, bps);
-  } else if (type >= 8 && type <= 12) {
-    int order = type - 8;
-    if (order > blocksize) return FLAC_E_HEADER;
-    for (int i = 0; i < order; ++i) s[i] = br_s64(b, bps);
-    int rc = read_residual(b, s, blocksize, order);
-    if (rc) return rc;
-    uint64_t* u = (uint64_t*)s;                /* wrapping arithmetic, as in the LPC branch below */
-    for (int i = order; i < blocksize; ++i) {
-      switch (order) {
-        case 0: break;
-        case 1: u[i] += u[i-1]; break;
-        case 2: u[i] += 2 * u[i-1] - u[i-2]; break;
-        case 3: u[i] += 3 * u[i-1] - 3 * u[i-2] + u[i-3]; break;
-        case 4: u[i] += 4 * u[i-1] - 6 * u[i-2] + 4 * u[i-3] - u[i-4]; break;
-      }
-    }
-  } else if (type >= 32) {
-    int order = (type & 31) + 1;
-    if (order > blocksize) return FLAC_E_HEADER;
-    for (int i = 0; i < order; ++i) s[i] = br_s64(b, bps);
-    int prec = (int)br_u(b, 4) + 1;
-    if (prec == 16) return FLAC_E_HEADER;
-    int shift = br_s(b, 5);
-    if (shift < 0) return FLAC_E_UNSUP;
-    int32_t coef[32];
-    for (int i = 0; i < order; ++i) coef[i] = br_s(b, prec);
-    int rc = read_residual(b, s, blocksize, order);
-    if (rc) return rc;
-    for (int i = order; i < blocksize; ++i) {
-      /* wrapping arithmetic: a valid stream never overflows 64 bits here, a corrupt one must not be undefined
-         behaviour (its frame CRC / the MD5 reject it afterwards) */
-      uint64_t sum = 0;
-      for (int j = 0; j < order; ++j) sum += (uint64_t)(int64_t)coef[j] * (uint64_t)s[i - 1 - j];
-      s[i] = (int64_t)((uint64_t)s[i] + (uint64_t)((int64_t)sum >> shift));
-    }
-  } else {
-    return FLAC_E_UNSUP;      /* reserved subframe types */
-  }
-  if (wasted) for (int i = 0; i < blocksize; ++i) s[i] = (int64_t)((uint64_t)s[i] << wasted);
-  return b->eof ? FLAC_E_TRUNC : FLAC_OK;
-}
-
-/* ---------------------------------------------------------------- stream */
-int wh_flac_decode(const uint8_t* data, size_t size, int32_t** samples_out, int64_t* n_frames_out, int* channels_out,
-                   int* sample_rate_out, int* bps_out) {
-  if (!data || !samples_out || !n_frames_out || !channels_out || !sample_rate_out || !bps_out) return FLAC_E_HEADER;
-  *samples_out = NULL;
+static int parse_metadata(const uint8_t* data, size_t size, flac_info* fi) {
   size_t pos = 0;
   if (size >= 10 && !memcmp(data, "ID3", 3)) {        /* skip an ID3v2 tag */
     size_t tag = ((size_t)(data[6] & 127) << 21) | ((size_t)(data[7] & 127) << 14) | ((size_t)(data[8] & 127) << 7) | (data[9] & 127);
@@ -232,9 +100,8 @@ int wh_flac_decode(const uint8_t* data, size_t size, int32_t** samples_out, int6
   }
   if (pos + 4 > size || memcmp(data + pos, "fLaC", 4)) return FLAC_E_MAGIC;
   pos += 4;
-  int have_info = 0, sr = 0, ch = 0, bps = 0, max_block = 0;
-  uint64_t total = 0;
-  uint8_t md5_want[16];
+  int have_info = 0;
+  memset(fi, 0, sizeof *fi);
   for (;;) {
     if (pos + 4 > size) return FLAC_E_TRUNC;
     int last = data[pos] >> 7, type = data[pos] & 127;
@@ -244,18 +111,33 @@ int wh_flac_decode(const uint8_t* data, size_t size, int32_t** samples_out, int6
     if (type == 0) {
       if (len < 34) return FLAC_E_HEADER;
       const uint8_t* q = data + pos;
-      max_block = (q[2] << 8) | q[3];
-      sr = (q[10] << 12) | (q[11] << 4) | (q[12] >> 4);
-      ch = ((q[12] >> 1) & 7) + 1;
-      bps = (((q[12] & 1) << 4) | (q[13] >> 4)) + 1;
-      total = ((uint64_t)(q[13] & 15) << 32) | ((uint64_t)q[14] << 24) | ((uint64_t)q[15] << 16) | ((uint64_t)q[16] << 8) | q[17];
-      memcpy(md5_want, q + 18, 16);
+      fi->max_block = (q[2] << 8) | q[3];
+      fi->sr = (q[10] << 12) | (q[11] << 4) | (q[12] >> 4);
+      fi->ch = ((q[12] >> 1) & 7) + 1;
+      fi->bps = (((q[12] & 1) << 4) | (q[13] >> 4)) + 1;
+      fi->total = ((uint64_t)(q[13] & 15) << 32) | ((uint64_t)q[14] << 24) | ((uint64_t)q[15] << 16) | ((uint64_t)q[16] << 8) | q[17];
+      memcpy(fi->md5, q + 18, 16);
       have_info = 1;
     }
     pos += len;
     if (last) break;
   }
-  if (!have_info || sr == 0 || max_block < 16 || bps < 4 || bps > 32) return FLAC_E_HEADER;
+  if (!have_info || fi->sr == 0 || fi->max_block < 16 || fi->bps < 4 || fi->bps > 32) return FLAC_E_HEADER;
+  fi->first = pos;
+  return FLAC_OK;
+}
+
+/* ---------------------------------------------------------------- stream */
+int wh_flac_decode(const uint8_t* data, size_t size, int32_t** samples_out, int64_t* n_frames_out, int* channels_out,
+                   int* sample_rate_out, int* bps_out) {
+  if (!data || !samples_out || !n_frames_out || !channels_out || !sample_rate_out || !bps_out) return FLAC_E_HEADER;
+  *samples_out = NULL;
+  flac_info fi;
+  int rc = parse_metadata(data, size, &fi);
+  if (rc) return rc;
+  const int ch = fi.ch, bps = fi.bps;
+  const uint64_t total = fi.total;
+  size_t pos = fi.first;
 
   /* STREAMINFO's sample count sizes the output only as far as the file could possibly hold that much: a frame of
      constant subframes packs 65535 samples per channel into ~16 bytes, nothing packs more; the buffer grows anyway */
@@ -265,56 +147,19 @@ int wh_flac_decode(const uint8_t* data, size_t size, int32_t** samples_out, int6
   int64_t* work = (int64_t*)malloc((size_t)65536 * 8 * sizeof(int64_t));
   if (!out || !work) { free(out); free(work); return FLAC_E_MEM; }
   size_t done = 0;
-  int rc = FLAC_OK;
 
   while (pos + 2 <= size) {
-    if (!(data[pos] == 0xFF && (data[pos+1] & 0xFE) == 0xF8)) {
+    if (!flac_is_sync(data, size, pos)) {
       /* trailing bytes (e.g. an ID3v1 tag) end the stream; garbage in the middle is an error */
       if (total && done >= total) break;
-      if (size - pos <= 128) break;
+      if (size - pos <= FLAC_TAIL) break;
       rc = FLAC_E_SYNC; break;
     }
-    BR b; br_init(&b, data, size, pos);
-    br_u(&b, 15);
-    int variable = (int)br_u(&b, 1); (void)variable;
-    int bs_code = (int)br_u(&b, 4), sr_code = (int)br_u(&b, 4), ch_code = (int)br_u(&b, 4), ss_code = (int)br_u(&b, 3);
-    if (br_u(&b, 1)) { rc = FLAC_E_HEADER; break; }
-    /* UTF-8 style coded frame / sample number */
-    uint32_t first = br_u(&b, 8);
-    int ones = 0, extra = 0;
-    while (ones < 8 && (first & (0x80u >> ones))) ++ones;
-    if (ones == 1 || ones == 8) { rc = FLAC_E_HEADER; break; }
-    if (ones) extra = ones - 1;
-    for (int i = 0; i < extra; ++i) if ((br_u(&b, 8) & 0xC0) != 0x80) { rc = FLAC_E_HEADER; }
+    flac_hdr h; size_t end; int range = 0;
+    rc = flac_frame_w(data, size, pos, ch, bps, FLAC_MAX_BLOCK, work, 65536, 1, &h, &end, &range);
     if (rc) break;
-    int blocksize;
-    if (bs_code == 0) { rc = FLAC_E_HEADER; break; }
-    else if (bs_code == 1) blocksize = 192;
-    else if (bs_code <= 5) blocksize = 576 << (bs_code - 2);
-    else if (bs_code == 6) blocksize = (int)br_u(&b, 8) + 1;
-    else if (bs_code == 7) blocksize = (int)br_u(&b, 16) + 1;
-    else blocksize = 256 << (bs_code - 8);
-    if (sr_code == 12) br_u(&b, 8); else if (sr_code == 13 || sr_code == 14) br_u(&b, 16); else if (sr_code == 15) { rc = FLAC_E_HEADER; break; }
-    int fbps = bps;
-    switch (ss_code) { case 0: break; case 1: fbps = 8; break; case 2: fbps = 12; break; case 4: fbps = 16; break;
-                       case 5: fbps = 20; break; case 6: fbps = 24; break; case 7: fbps = 32; break; default: rc = FLAC_E_HEADER; }
-    if (rc) break;
-    int nch = ch_code < 8 ? ch_code + 1 : 2;
-    if (ch_code > 10 || nch != ch || fbps != bps || blocksize > 65535) { rc = ch_code > 10 ? FLAC_E_HEADER : FLAC_E_UNSUP; break; }
-    size_t hdr_end = br_bytepos(&b);
-    if (hdr_end + 1 > size) { rc = FLAC_E_TRUNC; break; }
-    if (crc8(data + pos, hdr_end - pos) != data[hdr_end]) { rc = FLAC_E_CRC; break; }
-    br_u(&b, 8);
-    for (int c = 0; c < nch && !rc; ++c) {
-      int side = (ch_code == 8 && c == 1) || (ch_code == 9 && c == 0) || (ch_code == 10 && c == 1);
-      rc = read_subframe(&b, work + (size_t)c * 65536, blocksize, bps + side);
-    }
-    if (rc) break;
-    br_align(&b);
-    size_t body_end = br_bytepos(&b);
-    if (body_end + 2 > size) { rc = FLAC_E_TRUNC; break; }
-    if (crc16(data + pos, body_end - pos) != (uint16_t)((data[body_end] << 8) | data[body_end + 1])) { rc = FLAC_E_CRC; break; }
-    pos = body_end + 2;
+    pos = end;
+    const int blocksize = h.blocksize;
 
     if (done + (size_t)blocksize > cap) {
       size_t ncap = cap * 2 > done + blocksize ? cap * 2 : done + blocksize;
@@ -322,16 +167,7 @@ int wh_flac_decode(const uint8_t* data, size_t size, int32_t** samples_out, int6
       if (!n) { rc = FLAC_E_MEM; break; }
       out = n; cap = ncap;
     }
-    int64_t* w0 = work; int64_t* w1 = work + 65536;
-    for (int i = 0; i < blocksize; ++i) {
-      if (ch_code == 8) w1[i] = w0[i] - w1[i];                       /* left, side  -> right = left - side */
-      else if (ch_code == 9) w0[i] = w0[i] + w1[i];                  /* side, right -> left = right + side */
-      else if (ch_code == 10) {                                      /* mid, side */
-        int64_t side = w1[i], mid = (int64_t)((uint64_t)w0[i] << 1) | (side & 1);
-        w0[i] = (mid + side) >> 1; w1[i] = (mid - side) >> 1;
-      }
-    }
-    for (int c = 0; c < nch; ++c) {
+    for (int c = 0; c < ch; ++c) {
       const int64_t* w = work + (size_t)c * 65536;
       for (int i = 0; i < blocksize; ++i) out[(done + i) * ch + c] = (int32_t)w[i];
     }
@@ -342,7 +178,7 @@ int wh_flac_decode(const uint8_t* data, size_t size, int32_t** samples_out, int6
   if (!rc) {
     if (total && done > total) done = total;
     int nonzero = 0;
-    for (int i = 0; i < 16; ++i) nonzero |= md5_want[i];
+    for (int i = 0; i < 16; ++i) nonzero |= fi.md5[i];
     if (nonzero) {                                                    /* an all-zero signature means "not computed" */
       MD5 m; md5_init(&m);
       const int nb = (bps + 7) / 8;
@@ -354,12 +190,114 @@ int wh_flac_decode(const uint8_t* data, size_t size, int32_t** samples_out, int6
       }
       md5_update(&m, buf, fill);
       uint8_t got[16]; md5_final(&m, got);
-      if (memcmp(got, md5_want, 16)) rc = FLAC_E_MD5;
+      if (memcmp(got, fi.md5, 16)) rc = FLAC_E_MD5;
     }
   }
   if (rc) { free(out); return rc; }
-  *samples_out = out; *n_frames_out = (int64_t)done; *channels_out = ch; *sample_rate_out = sr; *bps_out = bps;
+  *samples_out = out; *n_frames_out = (int64_t)done; *channels_out = ch; *sample_rate_out = fi.sr; *bps_out = bps;
   return FLAC_OK;
 }
 
 void wh_flac_free(int32_t* samples) { free(samples); }
+
+/* staging capacity (samples per channel) of the frame-parallel routes for a stream of `total` samples per channel: the
+ * stream itself and room for false candidates, each of which claims at most 65535 */
+uint64_t wh_flac_staging_frames(uint64_t total) { return total + total / 8 + 2 * 65536; }
+
+/* ---------------------------------------------------------------- the frame-parallel algorithm, run serially
+ * What csrc/flac.hip does on the GPU, stage by stage, from the same core: scan every byte offset for a frame header that
+ * holds, decode every candidate on its own into a staging buffer at the prefix sum of the candidates' block sizes, chain
+ * the candidates that belong to the stream, close the gaps the others left.  The STREAMINFO MD5 is not verified (it is
+ * serial over all PCM); every frame's CRC-8 and CRC-16, the unbroken chain and the sample count are.
+ * FLAC_E_UNSUP: a stream this route does not take (more than 24 bits per sample, no sample count in STREAMINFO);
+ * FLAC_E_REJECT: the stream fails its checks; metadata errors as wh_flac_decode reports them.
+ * stats (optional, int32[4]): candidates, chained frames, 1 if the staging buffer had to be compacted, 0.
+ * cand_* (optional, cand_cap entries each): the candidates' start offsets, block sizes, end offsets, decode statuses. */
+int wh_flac_decode_frames(const uint8_t* data, size_t size, int32_t** samples_out, int64_t* n_frames_out, int* channels_out,
+                          int* sample_rate_out, int* bps_out, int32_t* stats, int64_t* cand_start, int32_t* cand_bs,
+                          int64_t* cand_end, int32_t* cand_rc, int cand_cap) {
+  if (!data || !samples_out || !n_frames_out || !channels_out || !sample_rate_out || !bps_out) return FLAC_E_HEADER;
+  *samples_out = NULL;
+  if (stats) memset(stats, 0, 4 * sizeof(int32_t));
+  flac_info fi;
+  int rc = parse_metadata(data, size, &fi);
+  if (rc) return rc;
+  if (fi.bps > 24 || fi.total == 0) return FLAC_E_UNSUP;
+  const int ch = fi.ch;
+  const uint64_t cap = wh_flac_staging_frames(fi.total);
+
+  /* scan: candidates in offset order */
+  size_t n_cand = 0, room = 1024;
+  int64_t* start = (int64_t*)malloc(room * sizeof(int64_t));
+  int32_t* bs = (int32_t*)malloc(room * sizeof(int32_t));
+  if (!start || !bs) { free(start); free(bs); return FLAC_E_MEM; }
+  for (size_t pos = fi.first; pos + 2 <= size; ++pos) {
+    if (data[pos] != 0xFF) continue;
+    const int b = flac_candidate(data, size, pos, ch, fi.bps, fi.max_block);
+    if (!b) continue;
+    if (n_cand == room) {
+      room *= 2;
+      int64_t* ns = (int64_t*)realloc(start, room * sizeof(int64_t));
+      if (ns) start = ns;
+      int32_t* nb = (int32_t*)realloc(bs, room * sizeof(int32_t));
+      if (nb) bs = nb;
+      if (!ns || !nb) { free(start); free(bs); return FLAC_E_MEM; }
+    }
+    start[n_cand] = (int64_t)pos; bs[n_cand] = b; ++n_cand;
+  }
+  if (n_cand > 0x7fffffff) { free(start); free(bs); return FLAC_E_REJECT; }
+
+  /* provisional positions; candidates that do not fit the staging buffer are not decoded */
+  int64_t* end = (int64_t*)malloc((n_cand + 1) * sizeof(int64_t));
+  int64_t* prov = (int64_t*)malloc((n_cand + 1) * sizeof(int64_t));
+  int32_t* crc = (int32_t*)malloc((n_cand + 1) * sizeof(int32_t));
+  int32_t* acc = (int32_t*)malloc((n_cand + 1) * sizeof(int32_t));
+  uint64_t staged = 0;
+  for (size_t j = 0; j < n_cand && prov; ++j) { prov[j] = (int64_t)staged; staged += (uint64_t)bs[j]; }
+  if (staged > cap) staged = cap;
+  int32_t* out = (int32_t*)malloc((size_t)(staged ? staged : 1) * ch * sizeof(int32_t));
+  if (!end || !prov || !crc || !acc || !out) rc = FLAC_E_MEM;
+
+  /* decode: every candidate on its own */
+  for (size_t j = 0; j < n_cand && !rc; ++j) {
+    flac_hdr h; size_t e = (size_t)start[j]; int range = 0;
+    if ((uint64_t)prov[j] + (uint64_t)bs[j] > cap) crc[j] = FLAC_E_MEM;
+    else {
+      crc[j] = flac_frame_n(data, size, (size_t)start[j], ch, fi.bps, bs[j], out + (size_t)prov[j] * ch, 1, (size_t)ch, &h, &e, &range);
+      if (crc[j] == FLAC_OK && range) crc[j] = FLAC_E_RANGE;
+    }
+    end[j] = (int64_t)e;
+  }
+  if (!rc) {
+    const size_t nc = n_cand < (size_t)(cand_cap > 0 ? cand_cap : 0) ? n_cand : (size_t)(cand_cap > 0 ? cand_cap : 0);
+    if (cand_start) memcpy(cand_start, start, nc * sizeof(int64_t));
+    if (cand_bs) memcpy(cand_bs, bs, nc * sizeof(int32_t));
+    if (cand_end) memcpy(cand_end, end, nc * sizeof(int64_t));
+    if (cand_rc) memcpy(cand_rc, crc, nc * sizeof(int32_t));
+    if (stats) stats[0] = (int32_t)n_cand;
+  }
+
+  /* chain, then compact */
+  int n_acc = 0; int64_t done = 0;
+  if (!rc) {
+    const size_t tail_len = size < FLAC_TAIL ? size : FLAC_TAIL;
+    rc = flac_chain(start, end, bs, crc, (int)n_cand, fi.first, size, data + size - tail_len, fi.total, acc, &n_acc, &done);
+  }
+  if (!rc) {
+    if ((size_t)n_acc != n_cand) {
+      int64_t at = 0;
+      for (int k = 0; k < n_acc; ++k) {
+        const int j = acc[k];
+        if (prov[j] != at) memmove(out + (size_t)at * ch, out + (size_t)prov[j] * ch, (size_t)bs[j] * ch * sizeof(int32_t));
+        at += bs[j];
+      }
+      if (stats) stats[2] = 1;
+    }
+    if (stats) stats[1] = n_acc;
+    if ((uint64_t)done > fi.total) done = (int64_t)fi.total;
+  }
+  free(start); free(bs); free(end); free(prov); free(crc); free(acc);
+  if (rc) { free(out); return rc; }
+  *samples_out = out; *n_frames_out = done; *channels_out = ch; *sample_rate_out = fi.sr; *bps_out = fi.bps;
+  return FLAC_OK;
+}

@@ -418,6 +418,36 @@ hipError_t launch_resample(const void* pcm, int format, int bits, int channels, 
 // outputs one workgroup takes so that the input span they reach fits its LDS; 0: not even one fits (down / up too large)
 int resample_outputs_per_wg(int up, int down, int half);
 
+// ---- flac.hip ------------------------------------------------------------------------------
+// FLAC decoding, one lane per frame (stages and definitions at the top of flac.hip).  The scratch of one call, carved from one
+// allocation; hdr .. rc (record_bytes from the base) is what the host downloads for the chain.
+struct FlacScratch {
+  int* hdr;             // [0] candidates listed (<= max_cand), [1] candidates found
+  uint8_t* tail;        // the file's last min(size, 128) bytes
+  int64_t* start;       // [max_cand] candidate offsets, ascending
+  int64_t* end;         // [max_cand] offset behind the frame's CRC-16 (the start offset when the body did not parse)
+  int* bs;              // [max_cand] block size by the header
+  int* rc;              // [max_cand] decode status (flac_core.h: FLAC_OK, FLAC_E_*)
+  size_t record_bytes;
+  int64_t* prov;        // [max_cand] provisional position in the staging buffer, samples per channel
+  int* tile_count;
+  int* tile_base;
+  int64_t* mv_from;     // compaction list, uploaded after the chain
+  int64_t* mv_to;
+  int* mv_len;
+  int32_t* temp;        // [staging_frames][channels] second buffer of the compaction
+  size_t total_bytes;
+};
+FlacScratch flac_scratch(void* base, size_t size, int channels, int64_t staging_frames, int max_cand);
+// candidates of file[first, size) in offset order with their provisional positions (first < size)
+hipError_t launch_flac_scan(const uint8_t* file, size_t size, size_t first, int ch, int bps, int max_block, const FlacScratch& s,
+                            int max_cand, hipStream_t stream);
+// every listed candidate decoded into pcm [staging_frames][ch] at its provisional position; end / rc / tail filled
+hipError_t launch_flac_decode(const uint8_t* file, size_t size, int ch, int bps, const FlacScratch& s, int max_cand, int32_t* pcm,
+                              int64_t staging_frames, hipStream_t stream);
+// dst[mv_to[k] ..] = src[mv_from[k] ..], mv_len[k] samples, k < n_moves
+hipError_t launch_flac_move(const int32_t* src, int32_t* dst, const FlacScratch& s, int n_moves, hipStream_t stream);
+
 // ---- score.hip -----------------------------------------------------------------------------
 // Teacher-forced scoring without the logits.  xn [M][K] (element type, row stride ldx), W = tok_emb [V][K], target [M]
 // (device int32), 1 <= v_end <= V.  Per row m, over the columns v < v_end of logit = xn · Wᵀ:

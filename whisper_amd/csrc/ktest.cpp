@@ -266,4 +266,41 @@ int wht_dtw_open(const float* cost, const int* d_rows, const int* d_cols, const 
                                     path_len, (hipStream_t)stream);
 }
 
+// flac.hip, stage by stage on a caller-supplied scratch (flac_scratch layout, >= wht_flac_scratch_bytes).  wht_flac_scan: the
+// candidate list of file[first, size) -> host n_found [1] (all candidates; the list holds min(n_found, max_cand)), start / bs /
+// prov [max_cand].  wht_flac_decode (after wht_flac_scan on the same scratch): every listed candidate decoded into pcm
+// [staging_frames][ch] -> host end / rc [max_cand].  Both wait for the stream.
+size_t wht_flac_scratch_bytes(size_t size, int ch, int64_t staging_frames, int max_cand) {
+  return flac_scratch(nullptr, size, ch, staging_frames, max_cand).total_bytes;
+}
+int wht_flac_scan(const uint8_t* file, size_t size, size_t first, int ch, int bps, int max_block, int max_cand,
+                  int64_t staging_frames, void* scratch, int* n_found, int64_t* start, int* bs, int64_t* prov, void* stream) {
+  if (!file || !scratch || !n_found || !start || !bs || !prov || first >= size || max_cand < 1) return hipErrorInvalidValue;
+  const FlacScratch s = flac_scratch(scratch, size, ch, staging_frames, max_cand);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_flac_scan(file, size, first, ch, bps, max_block, s, max_cand, st);
+  if (e != hipSuccess) return e;
+  int hdr[2];
+  if ((e = hipMemcpyAsync(hdr, s.hdr, sizeof hdr, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  *n_found = hdr[1];
+  const size_t n = (size_t)hdr[0];
+  if ((e = hipMemcpy(start, s.start, n * 8, hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  if ((e = hipMemcpy(bs, s.bs, n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  return hipMemcpy(prov, s.prov, n * 8, hipMemcpyDeviceToHost);
+}
+int wht_flac_decode(const uint8_t* file, size_t size, int ch, int bps, int max_cand, int64_t staging_frames, int32_t* pcm,
+                    void* scratch, int64_t* end, int* rc, void* stream) {
+  if (!file || !scratch || !pcm || !end || !rc || max_cand < 1) return hipErrorInvalidValue;
+  const FlacScratch s = flac_scratch(scratch, size, ch, staging_frames, max_cand);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_flac_decode(file, size, ch, bps, s, max_cand, pcm, staging_frames, st);
+  if (e != hipSuccess) return e;
+  int n = 0;
+  if ((e = hipMemcpyAsync(&n, s.hdr, sizeof n, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  if ((e = hipMemcpy(end, s.end, (size_t)n * 8, hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  return hipMemcpy(rc, s.rc, (size_t)n * 4, hipMemcpyDeviceToHost);
+}
+
 }  // extern "C"

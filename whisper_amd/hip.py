@@ -10,7 +10,7 @@ import contextlib
 import ctypes as C
 import os
 import threading
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -105,6 +105,10 @@ SIGNATURES = {
     "wh_log_mel": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "wh_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                               C.c_void_p, C.c_int64, C.c_void_p]),
+    "wh_flac_device_scratch_bytes": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int64, C.c_int]),
+    "wh_flac_decode_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                        C.c_int64, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
     "wh_model_create": (C.c_int, [C.POINTER(Dims), C.c_int, C.POINTER(ModelWeights), C.POINTER(C.c_void_p)]),
     "wh_model_destroy": (None, [C.c_void_p]),
     "wh_encoder_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
@@ -181,9 +185,11 @@ def lib():
     return _LIB
 
 
+WH_ERR_WORKSPACE = 2
 WH_ERR_LIMIT = 5
 WH_ERR_HANDOFF = 6
 WH_RUNNING = 7                      # wh_task_poll: the loop begun with wh_task_*_begin has not ended yet
+WH_ERR_STREAM = 8                   # wh_flac_decode_device: the stream fails its checks
 
 
 def check(rc: int, what: str = "") -> None:
@@ -1112,6 +1118,57 @@ def resample(pcm: torch.Tensor, rate: int, sr: int = 16000, bits: Optional[int] 
         check(lib().wh_resample(x.data_ptr(), fmt, bits, channels, n, taps.data_ptr(), up, down, half, out.data_ptr(), n_out,
                                 stream_ptr(s)), "wh_resample")
     return out
+
+
+class FlacInfo(NamedTuple):
+    """what the host reads from a FLAC file's metadata for flac_decode_device (audio.parse_flac_info)"""
+    first_frame: int            # offset of the first frame
+    sample_rate: int
+    channels: int
+    bits_per_sample: int
+    total_samples: int          # per channel; 0 = not stated
+    min_block: int
+    max_block: int
+
+
+def flac_staging_frames(total: int) -> int:
+    """samples per channel of staging for a stream of `total`: the stream, and room for false candidates (each claims its
+    header's block size, at most 65535) — wh_flac_staging_frames of the host twin"""
+    return total + total // 8 + 2 * 65536
+
+
+def flac_decode_device(data: torch.Tensor, info: FlacInfo):
+    """A whole FLAC file as a uint8 tensor on the GPU -> (status, int32 PCM [n_frames][channels] on the GPU or None, stats):
+    wh_flac_decode_device (csrc/flac.hip), one lane per frame, on the calling thread's current stream.  The PCM equals
+    audio.decode_flac's bit for bit; the STREAMINFO MD5 is not verified (every frame's CRC-8 / CRC-16, the chain of frames and
+    the sample count are).  status 0, or what makes the caller take the host decoder: WH_ERR_LIMIT (more than 24 bits per
+    sample, no sample count in STREAMINFO), WH_ERR_WORKSPACE (more frame candidates than the block sizes of STREAMINFO let
+    expect) or WH_ERR_STREAM (the stream fails its checks).  stats: (candidates, chained frames, compacted).  HipError for
+    anything else."""
+    require_gpu(data.device)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise ValueError("flac_decode_device: the file must be a contiguous 1-D uint8 tensor")
+    size, total, ch = data.numel(), int(info.total_samples), int(info.channels)
+    if not 4 <= info.bits_per_sample <= 24 or total == 0:
+        return WH_ERR_LIMIT, None, (0, 0, 0)
+    staging = flac_staging_frames(total)
+    max_cand = min(1 << 24, total // max(16, int(info.min_block)) + size // 32768 + 1024)
+    with torch.cuda.device(data.device):
+        need = lib().wh_flac_device_scratch_bytes(size, ch, staging, max_cand)
+        if need == 0:
+            raise HipError("wh_flac_device_scratch_bytes: invalid argument")
+        scratch = torch.empty(need, dtype=torch.uint8, device=data.device)
+        pcm = torch.empty((staging, ch), dtype=torch.int32, device=data.device)
+        n, stats = C.c_int64(0), (C.c_int32 * 4)()
+        s = torch.cuda.current_stream(data.device)
+        rc = lib().wh_flac_decode_device(data.data_ptr(), size, info.first_frame, ch, info.bits_per_sample, info.max_block,
+                                         total, pcm.data_ptr(), staging, max_cand, C.byref(n), stats, scratch.data_ptr(), need,
+                                         stream_ptr(s))
+    stats = (stats[0], stats[1], stats[2])
+    if rc in (WH_ERR_LIMIT, WH_ERR_WORKSPACE, WH_ERR_STREAM):
+        return rc, None, stats
+    check(rc, "wh_flac_decode_device")
+    return 0, pcm[: n.value], stats
 
 
 def median_filter(x: torch.Tensor, width: int) -> torch.Tensor:

@@ -105,7 +105,7 @@ def transcribe_sharded(model, audios: Sequence[Any], dist=None, *, batch_size: i
     """Many files over many GPUs: every rank transcribes its cost-balanced share with `transcribe_batch` (windows of
     one file never leave their rank: seek and prompt depend on the previous window, transcribe.py:288-293,371-399);
     rank 0 returns the result dicts in input order, other ranks None.  All inputs must be of one kind (arrays or
-    paths) for the costs to be comparable.  `device_ingest`: every rank loads its files on its own GPU (transcribe_batch).
+    paths) for the costs to be comparable.  `device_ingest` (True / "decode"): every rank loads its files on its own GPU (transcribe_batch).
     `phrases` / `phrase_boost` among the keywords: one phrase list for all files, compiled on every rank (transcribe_batch);
     `no_repeat_ngram_size` / `repetition_penalty` among them as well: repetition control on every rank (transcribe)."""
     from .decoding import check_repetition
@@ -113,6 +113,6 @@ def transcribe_sharded(model, audios: Sequence[Any], dist=None, *, batch_size: i
     from .transcribe import transcribe_batch
     costs = [_audio_cost(a) for a in audios]
     if device_ingest:
-        kwargs = dict(kwargs, device_ingest=True)
+        kwargs = dict(kwargs, device_ingest=device_ingest)        # True, or "decode" (FLAC decoded on the GPU as well)
     return run_balanced(list(audios), costs, lambda part: transcribe_batch(model, part, batch_size=batch_size, **kwargs),
                         dist)

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 import tqdm
 
-from .audio import (FRAMES_PER_SECOND, HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, load_audio, log_mel_spectrogram,
+from .audio import (FRAMES_PER_SECOND, HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, ingest_options, load_audio, log_mel_spectrogram,
                     pad_or_trim)
 from dataclasses import replace
 
@@ -436,7 +436,8 @@ def transcribe(
     start,end,start,end,... ranges in seconds; `word_timestamps` adds per-word timing from cross-attention + DTW.
     `device_ingest: bool = False` (no counterpart in the reference, so it travels among the keywords and the parameter list
     stays the reference's): a file path is loaded with `audio.load_audio(path, device=model.device)` — WAV / FLAC are
-    down-mixed, resampled and quantised on the GPU; arrays and tensors are untouched.
+    down-mixed, resampled and quantised on the GPU; arrays and tensors are untouched.  `device_ingest="decode"`: FLAC files
+    are decoded on the GPU as well (`load_audio(..., decode_on_device=True)`: same samples, the STREAMINFO MD5 is not verified).
     `phrases` / `phrase_boost` (likewise among the keywords): phrases the decoder should prefer — a `phrases.PhraseList`, or a
     list of strings compiled with `phrase_boost` (default 3.0 logit units); applied to every window and every rung of the
     temperature ladder (phrases.py; inside the device-side loop for greedy decoding and sampling).
@@ -445,8 +446,9 @@ def transcribe(
     window and every rung of the temperature ladder (decoding.NoRepeatNGram / RepetitionPenalty; inside the device-side
     loop for greedy decoding and sampling).
     """
-    if decode_options.pop("device_ingest", False) and isinstance(audio, str):
-        audio = load_audio(audio, device=model.device)
+    ingest = ingest_options(decode_options.pop("device_ingest", False))
+    if ingest is not None and isinstance(audio, str):
+        audio = load_audio(audio, device=model.device, **ingest)
     return _Transcriber(
         model, verbose, temperature, compression_ratio_threshold, logprob_threshold, no_speech_threshold,
         condition_on_previous_text, initial_prompt, carry_initial_prompt, word_timestamps, prepend_punctuations,
@@ -490,7 +492,7 @@ def _prompt_batches(model: "Whisper", options: DecodingOptions, prompts: List[Op
     return [rows[at: at + batch_size] for rows in classes.values() for at in range(0, len(rows), batch_size)]
 
 
-def _load_all(audios, device: Optional[torch.device] = None) -> list:
+def _load_all(audios, device: Optional[torch.device] = None, decode_on_device: bool = False) -> list:
     """decode the inputs that are file paths concurrently (ffmpeg subprocesses / the native FLAC decoder release the
     GIL) instead of one after the other at the start of every file's state machine; arrays pass through untouched.
     `device` (device-side ingest): the pool only parses / decodes the files to their stored PCM; the upload and the
@@ -503,7 +505,8 @@ def _load_all(audios, device: Optional[torch.device] = None) -> list:
         from . import hip
         from .audio import _ingest_device, _ingest_host
         hip.require_gpu(torch.device(device))
-        host, finish = (lambda i: _ingest_host(out[i], SAMPLE_RATE)), (
+        # decode_on_device: the pool only reads a FLAC file; upload and decode run here, on the calling thread's stream
+        host, finish = (lambda i: _ingest_host(out[i], SAMPLE_RATE, True) if decode_on_device else _ingest_host(out[i], SAMPLE_RATE)), (
             lambda i, staged: _ingest_device(staged, out[i], SAMPLE_RATE, torch.device(device)))
     else:
         host, finish = (lambda i: load_audio(out[i])), (lambda i, samples: samples)
@@ -546,7 +549,8 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
     a larger `batch_size` (rows per decode chain, up to 24) over more groups when there are enough files: a wider chain streams
     the decoder's weights once for all its rows.  Worth it from about 2 * batch_size files on.
     `device_ingest`: file paths are loaded as `load_audio(path, device=model.device)` loads them (WAV / FLAC down-mixed,
-    resampled and quantised on the GPU); the host-side parsing / FLAC decoding stays on the loader threads.
+    resampled and quantised on the GPU); the host-side parsing / FLAC decoding stays on the loader threads.  `"decode"`: FLAC
+    files are only read by the loader threads and decoded on the GPU (`load_audio(..., decode_on_device=True)`).
     `phrases` / `phrase_boost`: as in `transcribe`; one phrase list for all files.  `no_repeat_ngram_size` /
     `repetition_penalty`: as in `transcribe`."""
     audios = list(audios)
@@ -572,6 +576,7 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
         return merged
     fixed = {k: kwargs.pop(k, default) for k, default in _WALK_DEFAULTS.items()}
     audios = list(audios)
+    ingest = ingest_options(device_ingest)
     if batch_size < 1:
         raise ValueError(f"batch_size must be at least 1 (got {batch_size})")
     if max_active_files is None:
@@ -584,7 +589,7 @@ def transcribe_batch(model: "Whisper", audios, *, batch_size: int = 24, max_acti
     def start(take: List[int]) -> list:
         """only the files admitted are decoded to PCM and hold a whole-file spectrogram on the device, so memory follows the
         window of active files, not the total audio duration"""
-        loaded = _load_all([audios[i] for i in take], model.device if device_ingest else None)
+        loaded = _load_all([audios[i] for i in take], model.device if ingest is not None else None, bool(ingest))
         mels = [None] * len(take)
         if detect:
             # language identification (transcribe.py:139-152) of the admitted files in batched passes instead of one
@@ -754,7 +759,8 @@ def transcribe_chunked(model: "Whisper", audio: Union[str, np.ndarray, torch.Ten
       * `clip_timestamps` cannot be combined with chunking (ValueError), nor can `min_chunk_s` outside (0, 30] or `guard_s`
         above 0.64 (the cut kernel's halo);
       * `verbose=True` prints the segments chunk by chunk in completion order, not in file order; there is no progress bar.
-    `device_ingest`: a file path is loaded with `load_audio(path, device=model.device)`, as in `transcribe`; `phrases` /
+    `device_ingest`: a file path is loaded with `load_audio(path, device=model.device)`, as in `transcribe` (`"decode"`: FLAC
+    decoded on the GPU as well); `phrases` /
     `phrase_boost` and `no_repeat_ngram_size` / `repetition_penalty` likewise.
 
     Returns the dict `transcribe` returns — `segments` concatenated in chunk order with `id` renumbered, `text` the
@@ -768,8 +774,9 @@ def transcribe_chunked(model: "Whisper", audio: Union[str, np.ndarray, torch.Ten
     fixed = {k: kwargs.pop(k, default) for k, default in _WALK_DEFAULTS.items()}
     _compile_phrases(model, kwargs)              # `phrases` / `phrase_boost`: as in `transcribe`, one list for all chunks
     _check_repetition(kwargs)
-    if device_ingest and isinstance(audio, str):
-        audio = load_audio(audio, device=model.device)
+    ingest = ingest_options(device_ingest)
+    if ingest is not None and isinstance(audio, str):
+        audio = load_audio(audio, device=model.device, **ingest)
     mel = log_mel_spectrogram(audio, model.dims.n_mels, padding=N_SAMPLES, device=model.device)
     plan = plan_chunks(mel, mel.shape[-1] - N_FRAMES, min_chunk_s, guard_s)
     chunks = [(a / FRAMES_PER_SECOND, b / FRAMES_PER_SECOND) for a, b in plan]
