@@ -227,7 +227,11 @@ enum {
    * (sattn8_kernel, csrc/xattn.hip; bit-identical to the two launches).  Opt-in since round 6: alone on the chip the two
    * forms take the same time, beside other decode chains the fused one is slower (its consumers spin for q / k / v), so
    * the default step keeps only the cross attention fused (where the K/V stream hides the projection). */
-  WH_TASK_FUSED_SELF = 32
+  WH_TASK_FUSED_SELF = 32,
+  /* decode step of 9 - 24 rows (fp16): keep the LayerNorm prologue in every LayerNorm projection, i.e. do not hand fp16(x - centre)
+   * from the residual epilogues to projections that apply LayerNorm behind their MFMAs (csrc/kernels.h, "LayerNorm behind the
+   * MFMAs").  For same-process A/B and tests: the two forms agree to rounding, not bit for bit. */
+  WH_TASK_LN_PROLOGUE = 64
 };
 /* The workspace holds the cross-attention K/V of n_audio segments, the self-attention cache of n_audio * n_group rows
  * and the step buffers.  WH_F16 tasks with n_group > 1 (beam search) additionally hold a transposed copy of the
@@ -354,6 +358,8 @@ int wh_task_position(const wh_task *t);
  * what = 1: number of bounded hand-off spins that ran out in that kernel since the task was created (always 0 on a
  * healthy device; reads device memory, i.e. synchronises `stream`).  what = 4: number of times wh_task_greedy /
  * wh_task_beam re-ran a loop on the two-launch kernels after such a time-out (the answers to 0, 2, 3 are 0 from then on).
+ * what = 5: LayerNorm projections per decoder layer that the last decode step issued with LayerNorm behind the MFMAs
+ * (WH_TASK_LN_PROLOGUE; 0 before the first step).
  * Negative on error. */
 int wh_task_info(wh_task *t, int what, void *stream);
 

@@ -47,15 +47,40 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&part_o, (size_t)R * H * 16 * 64 * 2)); fill_half(part_o, (size_t)R * H * 16 * 64, 1.0f);
   CK(hipMalloc(&part_ml, (size_t)R * H * 16 * 2 * 4)); fill_float(part_ml, (size_t)R * H * 16 * 2, 1.0f);
 
-  struct Case { const char* name; int pro, epi, Nn, K; size_t woff; };
+  // post: 1 = the LayerNorm projection in its PRO_LN_POST form (fp16(x - centre) in fragment order, LayerNorm behind the MFMAs);
+  //       2 = the residual producer also storing that copy (GemvArgs::xh / xc)
+  struct Case { const char* name; int pro, epi, Nn, K; size_t woff; int post; };
+  // the centred fp16 copy of xf (centre = row mean + 0.3) and the centres, for the PRO_LN_POST cases
+  half_t* xpost; float* xcen;
+  {
+    const int Rp = (R + 7) / 8 * 8;
+    std::vector<float> hx((size_t)R * D), hc(Rp, 0.f);
+    std::vector<half_t> hp((size_t)Rp * D, (half_t)0.f);
+    CK(hipMemcpy(hx.data(), xf, hx.size() * 4, hipMemcpyDeviceToHost));
+    for (int r = 0; r < R; ++r) {
+      double m = 0; for (int k = 0; k < D; ++k) m += hx[(size_t)r * D + k];
+      hc[r] = (float)(m / D) + 0.3f;
+      for (int k = 0; k < D; ++k) hp[whk::frag_index(r, k, D)] = (half_t)(hx[(size_t)r * D + k] - hc[r]);
+    }
+    CK(hipMalloc(&xpost, hp.size() * 2)); CK(hipMemcpy(xpost, hp.data(), hp.size() * 2, hipMemcpyHostToDevice));
+    CK(hipMalloc(&xcen, hc.size() * 4)); CK(hipMemcpy(xcen, hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
+  }
+  half_t* xh_out; CK(hipMalloc(&xh_out, (size_t)((R + 7) / 8 * 8) * D * 2));
   Case cases[] = {
-    {"LN->qkv (3D x D)", whk::PRO_LN, whk::EPI_STORE, 3 * D, D, 0},
-    {"plain->out resid (DxD)", whk::PRO_PLAIN, whk::EPI_RESID, D, D, (size_t)3 * D * D},
-    {"LN->cq store (DxD)", whk::PRO_LN, whk::EPI_STORE, D, D, (size_t)5 * D * D},
-    {"combine->cout resid", whk::PRO_COMBINE, whk::EPI_RESID, D, D, (size_t)4 * D * D},
-    {"LN->fc1 gelu (4D x D)", whk::PRO_LN, whk::EPI_GELU, 4 * D, D, (size_t)6 * D * D},
-    {"plain->fc2 resid (Dx4D)", whk::PRO_PLAIN, whk::EPI_RESID, D, 4 * D, (size_t)10 * D * D},
+    {"LN->qkv (3D x D)", whk::PRO_LN, whk::EPI_STORE, 3 * D, D, 0, 0},
+    {"LNpost->qkv (3D x D)", whk::PRO_LN_POST, whk::EPI_STORE, 3 * D, D, 0, 1},
+    {"plain->out resid (DxD)", whk::PRO_PLAIN, whk::EPI_RESID, D, D, (size_t)3 * D * D, 0},
+    {"plain->out resid + xh", whk::PRO_PLAIN, whk::EPI_RESID, D, D, (size_t)3 * D * D, 2},
+    {"LN->cq store (DxD)", whk::PRO_LN, whk::EPI_STORE, D, D, (size_t)5 * D * D, 0},
+    {"LNpost->cq store (DxD)", whk::PRO_LN_POST, whk::EPI_STORE, D, D, (size_t)5 * D * D, 1},
+    {"combine->cout resid", whk::PRO_COMBINE, whk::EPI_RESID, D, D, (size_t)4 * D * D, 0},
+    {"combine->cout resid + xh", whk::PRO_COMBINE, whk::EPI_RESID, D, D, (size_t)4 * D * D, 2},
+    {"LN->fc1 gelu (4D x D)", whk::PRO_LN, whk::EPI_GELU, 4 * D, D, (size_t)6 * D * D, 0},
+    {"LNpost->fc1 gelu (4D x D)", whk::PRO_LN_POST, whk::EPI_GELU, 4 * D, D, (size_t)6 * D * D, 1},
+    {"plain->fc2 resid (Dx4D)", whk::PRO_PLAIN, whk::EPI_RESID, D, 4 * D, (size_t)10 * D * D, 0},
+    {"plain->fc2 resid + xh", whk::PRO_PLAIN, whk::EPI_RESID, D, 4 * D, (size_t)10 * D * D, 2},
   };
+  std::vector<half_t> y_ln;      // the last PRO_LN case's output of one launch, for the PRO_LN_POST case that follows it
   // PROBE_FRAG=1: the PRO_PLAIN x rows in fragment order (kernels.h); checked once against the row-major launch
   // (the weights in fragment order were measured with an earlier form of this probe: profiles/r06_fragment_order.txt)
   const bool frag = getenv("PROBE_FRAG") && atoi(getenv("PROBE_FRAG")), fragx = frag;
@@ -65,7 +90,23 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&xh_frag, (size_t)Rp * 4 * D * 2)); CK(hipMemset(xh_frag, 0, (size_t)Rp * 4 * D * 2));
   }
   for (const Case& c : cases) for (int variant : {0, 99}) {
-    if (variant == 99 && (getenv("PROBE_MFMA_ONLY") || frag)) continue;
+    if (variant == 99 && (getenv("PROBE_MFMA_ONLY") || frag || c.post)) continue;
+    if (c.post && (R < 9 || R > 24)) continue;
+    if (variant == 0 && (c.pro == whk::PRO_LN || c.post == 1)) {
+      // one launch from the same x: the PRO_LN_POST outputs against the PRO_LN ones
+      whk::GemvArgs a; memset(&a, 0, sizeof(a));
+      a.pro = c.pro; a.xf = xf; a.xf_ld = D; a.ln_w = lnw; a.ln_b = lnb; a.ln_folded = 1; a.xh = xpost;
+      a.W = W + c.woff; a.bias = bias; a.N = c.Nn; a.K = c.K; a.R = R; a.epi = c.epi; a.y = y; a.y_ld = c.Nn;
+      CK(whk::launch_gemv(a, 1, st)); CK(hipStreamSynchronize(st));
+      std::vector<half_t> hy((size_t)R * c.Nn);
+      CK(hipMemcpy(hy.data(), y, hy.size() * 2, hipMemcpyDeviceToHost));
+      if (c.post && hy.size() == y_ln.size()) {
+        double md = 0, mv = 0;
+        for (size_t i = 0; i < hy.size(); ++i) { md = std::max(md, fabs((double)hy[i] - (double)y_ln[i])); mv = std::max(mv, fabs((double)y_ln[i])); }
+        printf("%-26s vs PRO_LN: max |diff| %.4g (max |y| %.4g)\n", c.name, md, mv);
+      }
+      if (!c.post) y_ln = hy;
+    }
     if (frag) {
       if (c.pro == whk::PRO_PLAIN) {
         std::vector<half_t> h((size_t)R * c.K), hf((size_t)((R + 7) / 8 * 8) * c.K, (half_t)0.f);
@@ -104,6 +145,8 @@ int main(int argc, char** argv) {
       if (fragx && c.pro == whk::PRO_PLAIN) { a.x = xh_frag; a.x_frag = 1; }
       a.w_ordered = getenv("PROBE_WORD") ? atoi(getenv("PROBE_WORD")) : 0;
       a.epi = c.epi; a.y = y; a.y_ld = c.Nn; a.resid = resid; a.resid_ld = D;
+      if (c.post == 1) a.xh = xpost;
+      if (c.post == 2) { a.xh = xh_out; a.xc = xcen; }
       a.probe = i == N - 1 ? d_probe : nullptr;
       a.variant = variant == 99 ? -1 : variant;      // -1: the v_dot2 kernels
       hipError_t e = whk::launch_gemv(a, 1, st);

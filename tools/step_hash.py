@@ -23,6 +23,9 @@ dims = dims_for(name)
 sd = synthetic_state_dict(dims, seed=0, device=dev)
 model = hip.HipModel(dims, hip.WH_F16, hip.pack_weights(sd, dims, hip.WH_F16, dev))
 model32 = hip.HipModel(dims, hip.WH_F32, hip.pack_weights(sd, dims, hip.WH_F32, dev)); del sd
+# STEP_HASH_TASK_FLAGS=64 (WH_TASK_LN_PROLOGUE): OR-ed into every task — the two settings agree to rounding, not bit for bit: compare
+# the `tokens` digests of the greedy leg
+model.debug_task_flags = model32.debug_task_flags = int(os.environ.get("STEP_HASH_TASK_FLAGS", "0"))
 tok = get_tokenizer(True, num_languages=dims.n_vocab - 51765 - 1, language="en", task="transcribe")
 init = list(tok.sot_sequence); T0 = len(init)
 suppress = sorted(set(list(tok.non_speech_tokens) + [tok.transcribe, tok.translate, tok.sot, tok.sot_prev, tok.sot_lm, tok.no_speech, tok.eot]))

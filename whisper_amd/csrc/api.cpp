@@ -320,6 +320,8 @@ struct wh_task {
   unsigned long long* so_gran;   // ... and for the attention outputs handed to attn.out inside the same launch
   int* merge_cnt;                // [R][H] tickets of the cross attention's in-launch merge (attention.hip), 0 between launches
   float* x2;                     // second residual-stream buffer: the fused self-attention launch reads x and writes x2 (or back)
+  int ln_post_sites;             // LayerNorm sites per layer the decode step runs with LayerNorm behind the MFMAs (step_plan)
+  void* xh; float* xcen;         // LayerNorm behind the MFMAs (kernels.h): fp16(x - centre) [R8][D] in fragment order, centres [R]
   bool fused_xattn, fused_sattn, fused_out;   // fused_out: attn.out + residual inside the self-attention launch (dev builds)
   bool fused_xout;               // attn.out + residual as phase 0 of the fused cross-attention launch (xattn.hip, OUT0)
   size_t total;
@@ -439,6 +441,8 @@ static void task_carve(wh_task* t, void* base) {
   t->d_tick = (int*)c.take(256);
   t->d_err = t->d_tick + 16;
   t->merge_cnt = (int*)c.take(R * H * 4);
+  t->xh = c.take((R + 7) / 8 * 8 * D * 2);
+  t->xcen = (float*)c.take(R * 4);
   t->total = align_up(c.off, 256);
 }
 
@@ -527,6 +531,7 @@ extern "C" int wh_task_info(wh_task* t, int what, void* stream) {
   if (what == 2) return t->fused_sattn ? 1 : 0;
   if (what == 3) return (t->fused_out || t->fused_xout) ? 1 : 0;
   if (what == 4) return t->handoff_fallbacks;
+  if (what == 5) return t->ln_post_sites;
   if (what == 1) {                       // hand-off timeouts of the fused cross attention since the task was created
     if (t->needs_reset) return 0;
     int v = 0;
@@ -689,7 +694,12 @@ extern "C" int wh_task_set_audio(wh_task* t, const void* features, void* stream_
 //    (attention.hip: the last workgroup of a (row, head) to finish), so cross_attn.out is a plain projection without a merge
 //    prologue: 9 / 12 / 16 rows 1753 / 1816 / 1999 -> 1701 / 1770 / 1973 us per step.  At 17 - 24 rows the tickets of 1440
 //    workgroups cost more than the merge launch they replace (24 rows 2448 -> 2471): that launch stays.  A/B: WH_NO_TAIL_MERGE=1.
-struct StepPlan { bool frag_att, frag_self, frag_mlp, tail_merge; };
+//  * LayerNorm behind the MFMAs (kernels.h): at 9 - 24 rows a LayerNorm projection reads fp16(x - centre), stored in fragment order
+//    by the residual epilogue in front of it, where gemv.hip measured that form faster (gemv8_ln_post_pays: the one-slot shapes —
+//    of large-v3 the cross query).  post_cq / post_fc1: per LayerNorm site; LN -> QKV always keeps its LayerNorm prologue and
+//    leaves the exact row means as the centres of the layer's fp16 copies.  Never at <= 8 rows (the fused attention launches
+//    share that LayerNorm).  A/B: task flag WH_TASK_LN_PROLOGUE, WH_NO_LN_POST=1.
+struct StepPlan { bool frag_att, frag_self, frag_mlp, tail_merge, post_cq, post_fc1; };
 static StepPlan step_plan(const wh_task* t) {
   const wh_model* m = t->m;
   const int D = m->d.n_text_state, R = t->R;
@@ -701,6 +711,16 @@ static StepPlan step_plan(const wh_task* t) {
                gemv8_will_run(R, D, 4 * D, PRO_PLAIN);                                    // FC1 -> FC2
   p.tail_merge = m->dtype == WH_F16 && !t->fused_xattn && t->G == 1 && R <= 16 && t->cross_splits >= 2 &&
                  t->cross_splits <= 4 && !WH_DEV_FLAG("WH_NO_TAIL_MERGE");
+  const bool post_on = m->dtype == WH_F16 && (m->w.flags & WH_WEIGHTS_DEC_LN_FOLDED) && R >= 9 && R <= 24 &&
+                       !(t->flags & WH_TASK_LN_PROLOGUE) && !WH_DEV_FLAG("WH_NO_LN_POST") && !t->fused_xattn && !t->fused_sattn &&
+                       !t->fused_xout;
+  // ... and only behind a residual epilogue of gemv8_kernel (a merge prologue there: 2 - 4 splits)
+  auto resid_gemv8 = [&](int splits) {
+    return splits <= 1 ? gemv8_will_run(R, D, D, PRO_PLAIN) : splits <= 4 && gemv8_will_run(R, D, D, PRO_COMBINE);
+  };
+  const bool cross_merged = p.tail_merge || (R > 16 && !WH_DEV_FLAG("WH_NO_MERGE_KERNEL"));      // launch_cross_out
+  p.post_cq = post_on && gemv8_will_run(R, 3 * D, D, PRO_LN) && gemv8_ln_post_pays(R, D, D) && resid_gemv8(t->self_splits);
+  p.post_fc1 = post_on && gemv8_will_run(R, 3 * D, D, PRO_LN) && gemv8_ln_post_pays(R, 4 * D, D) && resid_gemv8(cross_merged ? 1 : t->cross_splits);
   return p;
 }
 
@@ -710,6 +730,15 @@ static GemvArgs ln_proj(const wh_model* m, const float* x, int rows, const float
   GemvArgs g; memset(&g, 0, sizeof(g));
   g.pro = PRO_LN; g.xf = x; g.xf_ld = K; g.ln_w = ln_w; g.ln_b = ln_b; g.ln_folded = (m->w.flags & WH_WEIGHTS_DEC_LN_FOLDED) ? 1 : 0;
   g.W = W; g.bias = bias; g.N = N; g.K = K; g.R = rows;
+  return g;
+}
+// a LayerNorm site of the decode step.  post: LayerNorm behind the MFMAs on the task's fp16 copy (left by the residual epilogue in
+// front of this launch); publish (LayerNorm prologue only): leave the row means as the centres of the copies made behind it
+static GemvArgs ln_site(const wh_task* t, bool post, bool publish, const float* x, const float* ln_w, const float* ln_b,
+                        const void* W, const float* bias, int N) {
+  GemvArgs g = ln_proj(t->m, x, t->R, ln_w, ln_b, W, bias, N, t->m->d.n_text_state);
+  if (post) { g.pro = PRO_LN_POST; g.xh = t->xh; }
+  if (publish) g.xc = t->xcen;
   return g;
 }
 // the decoder's last LayerNorm -> token embedding (never folded: the matrix is the embedding table too), fp32 logits
@@ -735,8 +764,10 @@ static hipError_t gemv_store(const wh_model* m, GemvArgs g, int epi, void* y, in
   g.epi = epi; g.y = y; g.y_ld = y_ld; g.y_frag = y_frag;
   return launch_gemv(g, m->dtype, s);
 }
-static hipError_t gemv_resid(const wh_model* m, GemvArgs g, float* resid, hipStream_t s) {
+// post_next (the task): the LayerNorm site behind this launch reads the fp16 copy of the new residual rows
+static hipError_t gemv_resid(const wh_model* m, GemvArgs g, float* resid, hipStream_t s, const wh_task* post_next = nullptr) {
   g.epi = EPI_RESID; g.resid = resid; g.resid_ld = g.N;
+  if (post_next) { g.xh = post_next->xh; g.xc = post_next->xcen; }
   return launch_gemv(g, m->dtype, s);
 }
 
@@ -772,6 +803,7 @@ static DecAttnArgs cross_attn_args(const wh_task* t, int l, const void* q, int r
 }
 // resid += cross_attn.out of the decode step: where the attention launch left its partials decides the prologue
 static int launch_cross_out(const wh_task* t, const StepPlan& plan, const wh_layer_weights& L, float* resid, hipStream_t s) {
+  const wh_task* post_next = plan.post_fc1 ? t : nullptr;
   const wh_model* m = t->m;
   const int D = m->d.n_text_state, R = t->R;
   // 17+ rows (beam search): the projection runs as 16-row workgroups that would each merge their rows' partials
@@ -785,7 +817,7 @@ static int launch_cross_out(const wh_task* t, const StepPlan& plan, const wh_lay
     HIPCHK(launch_merge_partials(t->part_o, t->part_ml, splits, R, m->d.n_text_head, t->att, D, m->dtype, s, plan.frag_att));
     splits = 1; frag = plan.frag_att;
   }
-  HIPCHK(gemv_resid(m, plain_proj(t, t->att, D, frag, splits, R, L.cout_w, L.cout_b, D, D), resid, s));
+  HIPCHK(gemv_resid(m, plain_proj(t, t->att, D, frag, splits, R, L.cout_w, L.cout_b, D, D), resid, s, post_next));
   return WH_OK;
 }
 
@@ -1051,6 +1083,7 @@ static int step_launch(wh_task* t, hipStream_t s, bool embedded = false) {
   float* xc = t->x;
   float* xo = t->x2;
   const StepPlan plan = step_plan(t);
+  t->ln_post_sites = (int)plan.post_cq + (int)plan.post_fc1;
   for (int l = 0; l < d.n_text_layer; ++l) {
     const wh_layer_weights& L = m->dec[l];
     bool out_done = false;
@@ -1060,7 +1093,7 @@ static int step_launch(wh_task* t, hipStream_t s, bool embedded = false) {
       if (t->fused_out) { float* tmp = xc; xc = xo; xo = tmp; out_done = true; }
     } else {
       // LN -> QKV, K/V appended in place at *d_pos
-      GemvArgs g = ln_proj(m, xc, R, L.attn_ln_w, L.attn_ln_b, L.qkv_w, L.qkv_b, 3 * D, D);
+      GemvArgs g = ln_site(t, false, plan.post_cq || plan.post_fc1, xc, L.attn_ln_w, L.attn_ln_b, L.qkv_w, L.qkv_b, 3 * D);
       g.epi = EPI_QKV; g.y = t->qbuf; g.y_ld = D;
       g.kcache = self_k_layer(t, l); g.vcache = self_v_layer(t, l); g.cache_bs = (int64_t)C * D; g.d_pos = t->d_pos; g.D = D;
       g.lag = t->d_lag;
@@ -1069,20 +1102,21 @@ static int step_launch(wh_task* t, hipStream_t s, bool embedded = false) {
     }
     if (t->fused_xout) out_done = true;       // attn.out + residual run as phase 0 of the cross-attention launch below
     if (!out_done)
-      HIPCHK(gemv_resid(m, plain_proj(t, t->att, D, plan.frag_self, t->self_splits, R, L.out_w, L.out_b, D, D), xc, s));
+      HIPCHK(gemv_resid(m, plain_proj(t, t->att, D, plan.frag_self, t->self_splits, R, L.out_w, L.out_b, D, D), xc, s,
+                        plan.post_cq ? t : nullptr));
     if (t->fused_xattn) {
       // LN -> cross query -> cross attention as ONE launch: the K/V stream starts at kernel entry, the projection runs
       // under it and reaches the K/V waves through tagged granules (xattn.hip)
       HIPCHK(launch_xattn8(xattn_args(t, l, 0, xc, t->fused_xout), s));
     } else {
       // LN -> cross query
-      HIPCHK(gemv_store(m, ln_proj(m, xc, R, L.cross_ln_w, L.cross_ln_b, L.cq_w, L.cq_b, D, D), EPI_STORE, t->qbuf, D, false, s));
+      HIPCHK(gemv_store(m, ln_site(t, plan.post_cq, false, xc, L.cross_ln_w, L.cross_ln_b, L.cq_w, L.cq_b, D), EPI_STORE, t->qbuf, D, false, s));
       HIPCHK(launch_attn_decode(cross_attn_args(t, l, t->qbuf, R, t->G, t->cross_splits, &plan), m->dtype, s));
     }
     const int rc = launch_cross_out(t, plan, L, xc, s);
     if (rc != WH_OK) return rc;
     // LN -> MLP
-    HIPCHK(gemv_store(m, ln_proj(m, xc, R, L.mlp_ln_w, L.mlp_ln_b, L.fc1_w, L.fc1_b, 4 * D, D), EPI_GELU, t->h, 4 * D, plan.frag_mlp, s));
+    HIPCHK(gemv_store(m, ln_site(t, plan.post_fc1, false, xc, L.mlp_ln_w, L.mlp_ln_b, L.fc1_w, L.fc1_b, 4 * D), EPI_GELU, t->h, 4 * D, plan.frag_mlp, s));
     HIPCHK(gemv_resid(m, plain_proj(t, t->h, 4 * D, plan.frag_mlp, 1, R, L.fc2_w, L.fc2_b, D, 4 * D), xc, s));
   }
   GemvArgs g = logits_proj(m, xc, R, t->logits, V);
@@ -1619,11 +1653,12 @@ static int bench_issue(wh_task* t, int kind, int iters, double* bytes_per_launch
         bytes = (double)R * t->pos * 2.0 * D * es;
       } break;
       case 3:
-        HIPCHK(gemv_store(m, ln_proj(m, t->x, R, L.attn_ln_w, L.attn_ln_b, L.qkv_w, L.qkv_b, 3 * D, D), EPI_STORE, t->qkv, 3 * D, false, s));
+        HIPCHK(gemv_store(m, ln_site(t, false, plan.post_cq || plan.post_fc1, t->x, L.attn_ln_w, L.attn_ln_b, L.qkv_w, L.qkv_b, 3 * D), EPI_STORE, t->qkv, 3 * D, false, s));
         bytes = 3.0 * D * D * es;
         break;
       case 4:
-        HIPCHK(gemv_store(m, ln_proj(m, t->x, R, L.mlp_ln_w, L.mlp_ln_b, L.fc1_w, L.fc1_b, 4 * D, D), EPI_GELU, t->h, 4 * D, plan.frag_mlp, s));
+        // (with LayerNorm behind its MFMAs the launch reads the fp16 copy the last step left)
+        HIPCHK(gemv_store(m, ln_site(t, plan.post_fc1, false, t->x, L.mlp_ln_w, L.mlp_ln_b, L.fc1_w, L.fc1_b, 4 * D), EPI_GELU, t->h, 4 * D, plan.frag_mlp, s));
         bytes = 4.0 * D * D * es;
         break;
       case 5:

@@ -779,7 +779,8 @@ template <int PRO, int GS, int KS, int NU, int CSm, int XW, int NRT>
 __global__ __launch_bounds__((GS * KS + XW) * 64) void gemv8_kernel(whk::GemvArgs a, int fw) {
   pin_kernargs(a);
   asm volatile("" ::"s"(fw));
-  static_assert((PRO == whk::PRO_PLAIN) == (XW == 0), "prologue waves exist exactly when there is a prologue");
+  constexpr bool POST = PRO == whk::PRO_LN_POST;           // LayerNorm applied in the epilogue (kernels.h "LayerNorm behind the MFMAs")
+  static_assert((PRO == whk::PRO_PLAIN || POST) == (XW == 0), "prologue waves exist exactly when there is a prologue");
   static_assert(PRO != whk::PRO_LN || KS == 4 || KS == 2, "LayerNorm prologue: one wave-load of fp32 = 256 elements = 4 K blocks");
   constexpr int MW = GS * KS;                              // weight (MFMA) waves; XW prologue waves in front of them
   constexpr int NT = (MW + XW) * 64;
@@ -791,6 +792,9 @@ __global__ __launch_bounds__((GS * KS + XW) * 64) void gemv8_kernel(whk::GemvArg
   // (FC2: 7.65 -> 7.30 us at 24 rows, 5.80 -> 5.44 at 8; the 4-wave and LayerNorm shapes lose 0.1 - 0.3 us, tools/probe_gemv8)
   constexpr bool W_ORDERED_OK = PRO == whk::PRO_PLAIN && KS == 16;
   __shared__ __attribute__((aligned(16))) half8v turn[W_ORDERED_OK ? MW : 1][64];   // one wave-load per weight wave
+  // POST: per weight wave, over its K split: [row tile][sum xc, sum xc^2][row] and the sums of its 8 weight rows
+  __shared__ float xstat[POST ? MW : 1][NRT][2][8];
+  __shared__ float wsum[POST ? MW : 1][8];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool is_x = wave < XW;                             // wave-uniform role
@@ -826,13 +830,13 @@ __global__ __launch_bounds__((GS * KS + XW) * 64) void gemv8_kernel(whk::GemvArg
       int blk = kw + KS * u; if (blk > nblk - 1) blk = nblk - 1;          // wave-uniform; clamped, masked through x == 0
       wa[u] = WH_WEIGHT_LOAD((const half8v*)((const char*)a.W + (size_t)blk * 128 + lane_off));
     }
-    if (PRO == whk::PRO_PLAIN) {
-      if (a.x_frag) {
+    if (PRO == whk::PRO_PLAIN || POST) {
+      if (POST || a.x_frag) {
         // fragment-order rows: unit (row tile, K block) = 1 KB, lane-linear (rows beyond R hold whatever the producer left:
         // they only reach output columns that are dropped)
 #pragma unroll
         for (int rt = 0; rt < NRT; ++rt) {
-          const char* tile = (const char*)a.x + (size_t)((r0 >> 3) + rt) * nblk * 1024 + (uint32_t)lane * 16u;
+          const char* tile = (const char*)(POST ? a.xh : a.x) + (size_t)((r0 >> 3) + rt) * nblk * 1024 + (uint32_t)lane * 16u;
 #pragma unroll
           for (int u = 0; u < NU; ++u) {
             int blk = kw + KS * u; if (blk > nblk - 1) blk = nblk - 1;
@@ -892,6 +896,7 @@ __global__ __launch_bounds__((GS * KS + XW) * 64) void gemv8_kernel(whk::GemvArg
             sum += ((j * 64 + lane) * 4 < K) ? t : 0.f;
           }
           const float mean = wave_sum(sum) * invK;
+          if (a.xc && blockIdx.x == 0 && lane == 0 && r < R) a.xc[r0 + r] = mean;      // the centre of the next LN site's fp16 copy
           float ss = 0.f;
 #pragma unroll
           for (int j = 0; j < NJ; ++j) {
@@ -985,7 +990,7 @@ __global__ __launch_bounds__((GS * KS + XW) * 64) void gemv8_kernel(whk::GemvArg
   // ---- epilogue operands (L2 hits, needed last; requested behind every wave's own loads): output o = tid + NT j ->
   // (slot, row tile, row, feature)
   constexpr int NOUT = (GS * NRT * 64 + NT - 1) / NT;
-  float e_bias[NOUT], e_res[NOUT];
+  float e_bias[NOUT], e_res[NOUT], e_cen[NOUT];
   int e_lag[NOUT];
   int e_pos = 0;
   if (a.epi == whk::EPI_QKV) e_pos = load_agent_int(a.d_pos);
@@ -995,12 +1000,13 @@ __global__ __launch_bounds__((GS * KS + XW) * 64) void gemv8_kernel(whk::GemvArg
     const int es = o / (NRT * 64), ert = (o >> 6) % NRT, er = (o >> 3) & 7, ej = o & 7;
     const int en = blockIdx.x * fw + es * 8 + ej;
     const bool on = o < GS * NRT * 64 && ert * 8 + er < R && es * 8 + ej < fw && en < a.N;
-    e_bias[j] = 0.f; e_res[j] = 0.f; e_lag[j] = 0;
+    e_bias[j] = 0.f; e_res[j] = 0.f; e_cen[j] = 0.f; e_lag[j] = 0;
     if (on) {
       const int64_t rr = r0 + ert * 8 + er;
       if (a.epi == whk::EPI_QKV && a.lag) e_lag[j] = a.lag[rr];
       if (a.bias) e_bias[j] = a.bias[en];
       if (a.epi == whk::EPI_RESID) e_res[j] = a.resid[rr * a.resid_ld + en];
+      if (a.epi == whk::EPI_RESID && a.xh) e_cen[j] = a.xc[rr];      // the centre of the fp16 copy this launch stores
     }
   }
   if (!XW) WH_PROBE_AT(a, wgid, 1);
@@ -1033,9 +1039,22 @@ __global__ __launch_bounds__((GS * KS + XW) * 64) void gemv8_kernel(whk::GemvArg
       }
     }
     const bool diag = (lane >> 5) == ((lane >> 3) & 1);
+    // POST: this lane's share of sum xc / sum xc^2 of row lane % 8 per row tile and of the sum of weight row lane % 8, taken from the
+    // very fp16 operands of the MFMAs (the correction then removes exactly the mean that was multiplied in); the v_dot2 run under
+    // the MFMAs of the same tile
+    float s1[NRT], s2[NRT], sw = 0.f;
+    half8v ones;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ones[e] = (half_t)1.f;
+    if constexpr (POST) {
+#pragma unroll
+      for (int u = 0; u < NU; ++u)
+        if (kw + KS * u < nblk) sw = dot_unit(wa[u], ones, sw);
+    }
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt) {
       float4v acc = {0.f, 0.f, 0.f, 0.f};
+      s1[rt] = 0.f; s2[rt] = 0.f;
       if constexpr (XW != 0) {
         half8v xt[NU];
 #pragma unroll
@@ -1045,6 +1064,10 @@ __global__ __launch_bounds__((GS * KS + XW) * 64) void gemv8_kernel(whk::GemvArg
       } else {
 #pragma unroll
         for (int u = 0; u < NU; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[u], xb[rt][u], acc, 0, 0, 0);
+        if constexpr (POST) {
+#pragma unroll
+          for (int u = 0; u < NU; ++u) { s1[rt] = dot_unit(xb[rt][u], ones, s1[rt]); s2[rt] = dot_unit(xb[rt][u], xb[rt][u], s2[rt]); }
+        }
       }
       // lane holds C[m = 4 (lane >> 4) + e][n = lane & 15]; valid where (m >> 3) == (n >> 3)
 #pragma unroll
@@ -1059,6 +1082,17 @@ __global__ __launch_bounds__((GS * KS + XW) * 64) void gemv8_kernel(whk::GemvArg
         for (int e = 0; e < 4; ++e) red[mw][rt][4 * (lane >> 4) + e][lane & 7] = acc[e];
       }
     }
+    if constexpr (POST) {
+      // lanes 8 j + i, j = 0..7, hold the shares of row i: exact exchanges over xor 8 / 16 / 32
+      sw = across_groups8_sum(sw);
+#pragma unroll
+      for (int rt = 0; rt < NRT; ++rt) { s1[rt] = across_groups8_sum(s1[rt]); s2[rt] = across_groups8_sum(s2[rt]); }
+      if (lane < 8) {
+        wsum[mw][lane] = sw;
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt) { xstat[mw][rt][0][lane] = s1[rt]; xstat[mw][rt][1][lane] = s2[rt]; }
+      }
+    }
   }
   WH_PROBE_AT(a, wgid, 4);
   __syncthreads();
@@ -1070,16 +1104,29 @@ __global__ __launch_bounds__((GS * KS + XW) * 64) void gemv8_kernel(whk::GemvArg
     const int en = blockIdx.x * fw + es * 8 + ej;
     const bool on = o < GS * NRT * 64 && ert * 8 + er < R && es * 8 + ej < fw && en < a.N;
     if (on) {
-      float v = e_bias[j];
+      float v = POST ? 0.f : e_bias[j];
 #pragma unroll
       for (int k = 0; k < KS; ++k) v += red[es * KS + k][ert][ej][er];
       const int64_t rr = r0 + ert * 8 + er;
       const int n = en;
+      if constexpr (POST) {
+        float t1 = 0.f, t2 = 0.f, tw = 0.f;
+#pragma unroll
+        for (int k = 0; k < KS; ++k) { t1 += xstat[es * KS + k][ert][0][er]; t2 += xstat[es * KS + k][ert][1][er]; tw += wsum[es * KS + k][ej]; }
+        const float invK = 1.0f / (float)K;
+        const float mc = t1 * invK;                                       // mean of the centred row
+        const float var = fmaxf(__builtin_fmaf(-mc, mc, t2 * invK), 0.f);
+        v = __builtin_fmaf(rsqrtf(var + 1e-5f), __builtin_fmaf(-mc, tw, v), e_bias[j]);
+      }
       switch (a.epi) {
         case whk::EPI_STORE: ((half_t*)a.y)[a.y_frag ? frag_elem(rr, n, a.N) : rr * a.y_ld + n] = (half_t)v; break;
         case whk::EPI_GELU: ((half_t*)a.y)[a.y_frag ? frag_elem(rr, n, a.N) : rr * a.y_ld + n] = (half_t)gelu_erf(v); break;
         case whk::EPI_F32: ((float*)a.y)[rr * a.y_ld + n] = v; break;
-        case whk::EPI_RESID: a.resid[rr * a.resid_ld + n] = e_res[j] + v; break;
+        case whk::EPI_RESID: {
+          const float xr = e_res[j] + v;
+          a.resid[rr * a.resid_ld + n] = xr;
+          if (a.xh) ((half_t*)a.xh)[frag_elem(rr, n, a.N)] = (half_t)fminf(fmaxf(xr - e_cen[j], -65504.f), 65504.f);
+        } break;
         case whk::EPI_QKV: {
           const int D = a.D;
           if (n < D) ((half_t*)a.y)[rr * a.y_ld + n] = (half_t)v;
@@ -1102,7 +1149,7 @@ hipError_t launch_gemv8_nrt(const whk::GemvArgs& a, int fw, hipStream_t stream) 
   constexpr int WAVES = GS * KS + XW;
   static_assert(WAVES <= 16, "at most 1024 threads per workgroup");
   if (fw < 1 || fw > 8 * GS) return hipErrorInvalidValue;
-  whk::g_form = WH_FORM_NAME("gemv8/%s/gs%d/ks%d/xw%d/rt%d", PRO == whk::PRO_PLAIN ? "plain" : PRO == whk::PRO_LN ? "LN" :
+  whk::g_form = WH_FORM_NAME("gemv8/%s/gs%d/ks%d/xw%d/rt%d", PRO == whk::PRO_PLAIN ? "plain" : PRO == whk::PRO_LN ? "LN" : PRO == whk::PRO_LN_POST ? "LNpost" :
                              CSm == 2 ? "combine2" : CSm == 3 ? "combine3" : "combine4", GS, KS, XW, NRT);
   const int nblk = a.K / 64;
   const int nu = (nblk + KS - 1) / KS;
@@ -1154,7 +1201,11 @@ static int gemv8_slots(int N, int pro) {
 template <int PRO, int CSm>
 hipError_t launch_gemv8_pro(const whk::GemvArgs& a, hipStream_t stream) {
   const int nblk = a.K / 64, gs = gemv8_slots(a.N, PRO), fw = gemv8_fw(a.N, gs);
-  if constexpr (PRO == whk::PRO_PLAIN) {
+  if constexpr (PRO == whk::PRO_LN_POST) {
+    // the plain 4-wave shape, one feature-group slot (gemv8_slots), 9..24 rows as 2 or 3 row tiles: every weight wave asks for its
+    // x fragments itself
+    return a.R <= 16 ? launch_gemv8_nrt<PRO, 1, 4, CSm, 0, 2>(a, fw, stream) : launch_gemv8_nrt<PRO, 1, 4, CSm, 0, 3>(a, fw, stream);
+  } else if constexpr (PRO == whk::PRO_PLAIN) {
     if (nblk > 20) {
       whk::GemvArgs b = a;
       b.w_ordered = !WH_DEV_FLAG("WH_GEMV8_W_OPERAND_ORDER");      // developer A/B: 1 = operand-order weight loads as everywhere else
@@ -1185,11 +1236,13 @@ bool gemv8_applies(const whk::GemvArgs& a) {
   if (a.variant != 0 || a.R < 1 || a.R > 96 || a.K % 64 != 0) return false;
   const int nblk = a.K / 64;
   if (nblk > 20 && (a.pro != whk::PRO_PLAIN || (nblk + 15) / 16 > 5)) return false;
+  if (a.xh && a.epi == whk::EPI_RESID && (a.N % 64 != 0 || !a.xc)) return false;   // the fp16 copy is a fragment-order activation of N columns
   if (a.epi == whk::EPI_F32 && a.N > 16384) return false;    // logits: the streaming kernels
   if ((int64_t)a.N * a.K >= (1ll << 31)) return false;       // 32-bit lane offsets, here and on R * ld below
   switch (a.pro) {
     case whk::PRO_PLAIN: return a.x_ld % 8 == 0 && (int64_t)a.R * a.x_ld < (1ll << 30);
     case whk::PRO_LN: return a.ln_folded && a.xf_ld % 4 == 0 && (int64_t)a.R * a.xf_ld < (1ll << 29);
+    case whk::PRO_LN_POST: return a.ln_folded && a.R > 8 && a.R <= WH_GEMV8_MAX_ROWS && a.R <= 24 && a.epi != whk::EPI_RESID;
     case whk::PRO_COMBINE:
       return a.K == a.H * 64 && a.H <= 20 && a.splits >= 2 && a.splits <= 4 && (int64_t)a.R * a.H * a.splits * 64 < (1ll << 29);
   }
@@ -1199,6 +1252,7 @@ bool gemv8_applies(const whk::GemvArgs& a) {
 hipError_t launch_gemv8(const whk::GemvArgs& a, hipStream_t stream) {      // only where gemv8_applies
   if (a.pro == whk::PRO_PLAIN) return launch_gemv8_pro<whk::PRO_PLAIN, 1>(a, stream);
   if (a.pro == whk::PRO_LN) return launch_gemv8_pro<whk::PRO_LN, 1>(a, stream);
+  if (a.pro == whk::PRO_LN_POST) return a.xh ? launch_gemv8_pro<whk::PRO_LN_POST, 1>(a, stream) : hipErrorInvalidValue;
   if (a.pro == whk::PRO_COMBINE && a.splits == 2) return launch_gemv8_pro<whk::PRO_COMBINE, 2>(a, stream);
   if (a.pro == whk::PRO_COMBINE && a.splits == 3) return launch_gemv8_pro<whk::PRO_COMBINE, 3>(a, stream);
   if (a.pro == whk::PRO_COMBINE && a.splits == 4) return launch_gemv8_pro<whk::PRO_COMBINE, 4>(a, stream);
@@ -1551,7 +1605,8 @@ Family pick_family(const whk::GemvArgs& a, int dtype) {
   if (a.R <= 0) return Family::refuse;
   // only gemv8_kernel knows the fragment order (kernels.h): a caller that asks for it where that kernel does not run must hear
   // about it (api.cpp::step_plan asks gemv8_will_run first) — never row-major arithmetic on fragment-order bytes
-  if (a.x_frag || a.y_frag) return dtype == 1 && a.R <= WH_GEMV8_MAX_ROWS && gemv8_applies(a) ? Family::gemv8 : Family::refuse;
+  if (a.xc && a.pro != whk::PRO_LN && !(a.xh && a.epi == whk::EPI_RESID)) return Family::refuse;   // nothing else reads or writes centres
+  if (a.x_frag || a.y_frag || a.pro == whk::PRO_LN_POST || a.xh || a.xc) return dtype == 1 && a.R <= WH_GEMV8_MAX_ROWS && gemv8_applies(a) ? Family::gemv8 : Family::refuse;
   // fp32 (strict-parity mode): x rows are twice as wide in LDS, and the 4-wave staging moves at most 24 units per
   // thread per row (K <= 3072 at 8 rows, K <= 6144 at 4 rows)
   if (dtype != 1) return a.R <= 4 || a.K > 3072 ? Family::rt4 : Family::rt8;
@@ -1614,6 +1669,18 @@ bool gemv8_will_run(int R, int N, int K, int pro) {
   a.pro = pro; a.R = R; a.N = N; a.K = K; a.x_ld = a.xf_ld = K; a.ln_folded = 1; a.splits = 2; a.H = K / 64;
   a.epi = EPI_STORE; a.y_frag = 1;
   return pick_family(a, 1) == Family::gemv8;
+}
+
+// PRO_LN_POST runs (gemv8_kernel, 9..24 rows) AND is the faster form of LayerNorm -> W [N][K].  Measured at 24 rows, large-v3
+// (tools/probe_gemv8 24, profiles/ln_post_ab.txt): the one-slot D x D shape (cross query) 5.97 -> 4.50 us; the shapes the
+// LayerNorm form runs with 2 / 3 feature-group slots lose — QKV 6.5 -> 6.7 us, FC1 6.6 -> 7.8 .. 8.4 us with every wave fetching
+// its x fragments, with one fetch per workgroup shared through LDS, and as one-slot workgroups alike: their time is the 40 / 60
+// operand-order weight wave-loads a workgroup pushes through its CU's address pipeline, which the LayerNorm waves' loads overlap
+// and the x fragments of the weight waves queue behind — so those keep PRO_LN.
+bool gemv8_ln_post_pays(int R, int N, int K) {
+  GemvArgs a = {};
+  a.pro = PRO_LN_POST; a.R = R; a.N = N; a.K = K; a.ln_folded = 1; a.epi = EPI_STORE;
+  return pick_family(a, 1) == Family::gemv8 && gemv8_slots(N, PRO_LN) == 1 && gemv8_will_run(R, N, K, PRO_LN);
 }
 
 hipError_t launch_merge_partials(const void* part_o, const float* part_ml, int splits, int R, int H, void* out,

@@ -218,7 +218,7 @@ bool sattn_supported(int D, int H, int R, int n_ctx);
 hipError_t launch_sattn8(const SAttnArgs& a, hipStream_t stream);
 
 // ---- gemv.hip ------------------------------------------------------------------------------
-enum { PRO_PLAIN = 0, PRO_LN = 1, PRO_COMBINE = 2 };
+enum { PRO_PLAIN = 0, PRO_LN = 1, PRO_COMBINE = 2, PRO_LN_POST = 3 };
 enum { EPI_STORE = 0, EPI_QKV = 1, EPI_RESID = 2, EPI_GELU = 3, EPI_F32 = 4 };
 struct GemvArgs {
   // prologue
@@ -234,6 +234,11 @@ struct GemvArgs {
   int x_frag;                                     // PRO_PLAIN: x holds FRAGMENT-ORDER rows (below), K columns; x_ld ignored
   int y_frag;                                     // EPI_STORE / EPI_GELU: write y in fragment order (N % 64 == 0); y_ld ignored
   int w_ordered;                                  // set by the launcher (gemv.hip): weight wave-loads in memory order + a turn through LDS
+  // LayerNorm applied AFTER the MFMAs (gemv8_kernel, fp16, folded LayerNorm, 9..24 rows; "LayerNorm behind the MFMAs" below):
+  //   PRO_LN with xc != null: workgroup 0 also stores the row means it computed into xc[R] — the centres;
+  //   EPI_RESID with xh != null also stores xh[frag_index(r, n, N)] = fp16(resid[r][n] - xc[r]), saturated to +-65504;
+  //   PRO_LN_POST reads xh in fragment order (K columns) instead of the fp32 rows (xc unused: LayerNorm does not see a shift).
+  void* xh; float* xc;
   // epilogue
   int epi;
   void* y; int64_t y_ld;                          // EPI_STORE / EPI_GELU (element type), EPI_F32 (float)
@@ -261,11 +266,24 @@ hipError_t launch_gemv(const GemvArgs& a, int dtype, hipStream_t stream);
 static inline int64_t frag_index(int r, int k, int K) {
   return ((((int64_t)(r >> 3) * (K >> 6) + (k >> 6)) * 64 + 16 * ((k & 31) >> 3) + 8 * ((k >> 5) & 1) + (r & 7)) << 3) + (k & 7);
 }
+// LayerNorm behind the MFMAs.  With the affine part folded into W' / b' (WH_WEIGHTS_DEC_LN_FOLDED) LayerNorm is linear once the
+// row statistics are known: for ANY per-row centre c, xc = x - c, m = mean_k(xc), v = mean_k(xc^2) - m^2, s_n = sum_k W'[n][k]:
+//   y[r][n] = b'[n] + rsqrt(v_r + 1e-5) * (sum_k W'[n][k] xc[r][k] - m_r s_n)
+// so an LN projection is a plain fragment-order projection on fp16(xc) whose statistics come out of the operands the weight waves
+// hold anyway: no fp32 rows, no prologue waves, no barrier in front of the MFMAs.  The producer of x (the residual epilogue of
+// attn.out / cross_attn.out / FC2) stores fp16(x - c) beside the fp32 residual.  Rounding x to fp16 loses the LayerNorm when
+// |mean| >> std, hence the centre: c_r is the exact fp32 row mean at the layer's FIRST LayerNorm site (LN -> QKV, which keeps the
+// LayerNorm prologue and has the mean in a register), stored by workgroup 0 of that launch into xc[r] and read by the producers
+// behind it in stream order — one or two sub-layer updates away from the row they centre, which is small next to the row.  The
+// centre is a function of the current step's data only: no state crosses steps, a captured step replays.  (A PRO_LN_POST launch
+// could pass c + m on, but the mean of fp16-rounded values is off by the mean rounding error, ~2e-4 std / sqrt(K).)
 // true when launch_gemv honours a fragment-order request for (R rows) x (N, K, pro), i.e. hands it to gemv8_kernel.  Asked about
 // the canonical launch of that shape: fp16, packed rows (x_ld = xf_ld = K), folded LayerNorm (PRO_LN: the caller checks
 // WH_WEIGHTS_DEC_LN_FOLDED itself), EPI_STORE, and for PRO_COMBINE splits = 2 and H = K / 64 heads.  A launch that differs
 // from it (padded rows, EPI_F32 with N > 16384, other split counts) may still be refused: gemv.hip, gemv8_applies.
 bool gemv8_will_run(int R, int N, int K, int pro);
+// true where LayerNorm -> W [N][K] at R rows runs as PRO_LN_POST and that form is the faster one (gemv.hip; api.cpp::step_plan)
+bool gemv8_ln_post_pays(int R, int N, int K);
 // the kernel family launch_gemv picks for `a`, decided without launching: "gemv8", "rows48", "rows48_stream", "rows16_mf", "rt4",
 // "rt8", or "" where it refuses (gemv.hip: pick_family; read by the kernel test library)
 const char* gemv_family(const GemvArgs& a, int dtype);

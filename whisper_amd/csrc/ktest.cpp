@@ -42,6 +42,33 @@ int wht_gemv(int dtype, int pro, const void* x, int64_t x_ld, const float* xf, i
   return launch_gemv(a, dtype, (hipStream_t)stream);
 }
 
+// LayerNorm behind the MFMAs (kernels.h) with explicit buffers.  Consumer: pro = PRO_LN_POST, xh = fp16(x - centre) in fragment
+// order, xc = centres [R] (replaced by the row means) or NULL.  Producer: a PRO_PLAIN / PRO_COMBINE launch with EPI_RESID that
+// also stores xh from xc.  First site: pro = PRO_LN with xc = where the row means go.  Every other argument as wht_gemv.
+int wht_gemv_ln_post(int pro, const void* x, int64_t x_ld, int x_frag, const float* xf, int64_t xf_ld, const void* part_o,
+                     const float* part_ml, int splits, int H, const void* W, const float* bias, int N, int K, int R, void* xh,
+                     float* xc, int y_frag, int epi, void* y, int64_t y_ld, float* resid, int64_t resid_ld, void* kcache,
+                     void* vcache, int64_t cache_bs, const int* d_pos, int D, const int* lag, void* stream) {
+  GemvArgs a;
+  memset(&a, 0, sizeof a);
+  a.pro = pro; a.x = x; a.x_ld = x_ld; a.x_frag = x_frag; a.xf = xf; a.xf_ld = xf_ld; a.ln_folded = 1;
+  a.part_o = part_o; a.part_ml = part_ml; a.splits = splits; a.H = H;
+  a.W = W; a.bias = bias; a.N = N; a.K = K; a.R = R; a.xh = xh; a.xc = xc; a.y_frag = y_frag;
+  a.epi = epi; a.y = y; a.y_ld = y_ld; a.resid = resid; a.resid_ld = resid_ld;
+  a.kcache = kcache; a.vcache = vcache; a.cache_bs = cache_bs; a.d_pos = d_pos; a.D = D; a.lag = lag;
+  return launch_gemv(a, 1, (hipStream_t)stream);
+}
+// the family of such a launch ("" = refused) and whether the decode step picks the form for LayerNorm -> W [N][K] at R rows
+const char* wht_gemv_family_ln_post(int dtype, int pro, int epi, int R, int N, int K, int ln_folded, int has_xh, int has_xc) {
+  static float some_f = 0.f;
+  GemvArgs a;
+  memset(&a, 0, sizeof a);
+  a.pro = pro; a.epi = epi; a.R = R; a.N = N; a.K = K; a.x_ld = a.xf_ld = K; a.ln_folded = ln_folded; a.splits = 2; a.H = K / 64;
+  a.xh = has_xh ? &some_f : nullptr; a.xc = has_xc ? &some_f : nullptr;
+  return gemv_family(a, dtype);
+}
+int wht_gemv8_ln_post_pays(int R, int N, int K) { return gemv8_ln_post_pays(R, N, K) ? 1 : 0; }
+
 int wht_merge_partials(const void* part_o, const float* part_ml, int splits, int R, int H, void* out, int64_t o_ld,
                        int dtype, int o_frag, void* stream) {
   return launch_merge_partials(part_o, part_ml, splits, R, H, out, o_ld, dtype, (hipStream_t)stream, o_frag);

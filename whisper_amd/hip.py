@@ -26,6 +26,7 @@ WH_TASK_TWO_LAUNCH_SELF = 2
 WH_TASK_TWO_LAUNCH_CROSS = 4
 WH_TASK_EXPIRE_HANDOFFS = 16        # fault injection (include/whisper_hip.h): every hand-off poll gives up at once
 WH_TASK_FUSED_SELF = 32             # opt-in: LN + QKV + cache append + self attention as one launch (sattn8_kernel)
+WH_TASK_LN_PROLOGUE = 64            # 9 - 24 rows: every LayerNorm projection keeps its LayerNorm prologue (A/B, tests)
 WH_WEIGHTS_DEC_LN_FOLDED = 1
 WH_WEIGHTS_ENC_QK_SCALED = 2
 # sqrt(0.125 * log2 e): with it in both the query and the key projection, K.Q^T is the exp2 argument of the softmax
@@ -832,6 +833,12 @@ class HipTask:
         """times wh_task_greedy / wh_task_beam re-ran a loop on the two-launch kernels after a hand-off time-out (the task
         stays on them afterwards: fused_cross_attention / fused_self_attention turn False)"""
         return lib().wh_task_info(self.handle, 4, None)
+
+    @property
+    def ln_post_sites(self) -> int:
+        """LayerNorm projections per decoder layer that the last decode step ran with LayerNorm behind the MFMAs
+        (csrc/kernels.h; 0 before the first step, at <= 8 or > 24 rows, and with WH_TASK_LN_PROLOGUE)"""
+        return lib().wh_task_info(self.handle, 5, None)
 
     def handoff_timeouts(self) -> int:
         """bounded hand-off spins of the fused cross attention that ran out (0 on a healthy device); synchronises"""
