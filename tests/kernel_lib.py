@@ -41,6 +41,17 @@ SIGNATURES = {
     "wht_beam_cand_offsets": (None, [_I, _I, ctypes.POINTER(_L), ctypes.POINTER(_L)]),
     "wht_beam_step": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P,
                            ctypes.c_size_t, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "wht_attn_generic": (_I, [_I, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _P, _I, _I, _P]),
+    "wht_cross_qk": (_I, [_P, _L, _P, _L, _I, _I, _I, _P, _I, _P]),
+    "wht_cross_qk_batch": (_I, [_P, _L, _L, _I, _P, _L, _L, _I, _P, _P, _I, _P, _I, _I, _I, _P, _I, _P]),
+    "wht_align_batch": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P, _I, _P, _P]),
+    "wht_dtw": (_I, [_P, _I, _I, _P, _P]),
+    "wht_dtw_batch": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
+    "wht_mel_transpose": (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),
+    "wht_embed": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _P]),
+    "wht_no_speech": (_I, [_P, _L, _I, _I, _I, _P, _P]),
+    "wht_gather_rows": (_I, [_P, _P, _I, _I, _P, _P]),
+    "wht_gather_tokens": (_I, [_P, _L, _I, _P, _P]),
 }
 
 _lib = None

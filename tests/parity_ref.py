@@ -1,7 +1,8 @@
 """Shared pieces of the per-element kernel parity suites (tests/test_kernel_parity_gpu.py, tests/test_fused_attn_parity_gpu.py):
 guarded device buffers, the ulp / rounding-flip / merge budgets and the float64 references of the LayerNorm-folded projection
 and of the split single-query attention.  Not a test module.  The reference functions run on whatever device their inputs
-are on (the attention reference on the CPU); with dtype == F64 nothing is rounded, which is the form
+are on (the attention reference on the CPU; prefill_align_ref.py, the sibling module of test_prefill_align_parity_gpu.py, builds its
+bounds from the constants and helpers here); with dtype == F64 nothing is rounded, which is the form
 tests/test_fused_attn_ref_cpu.py checks against oracle/model.py.  The bounds are derived in test_kernel_parity_gpu.py's
 module docstring."""
 import torch

@@ -388,6 +388,8 @@ hipError_t launch_beam_step(const BeamArgs& a, int B, hipStream_t stream);
 // ---- timing.hip ----------------------------------------------------------------------------
 hipError_t launch_median_filter(const float* x, float* out, int64_t rows, int n, int width,
                                 hipStream_t stream);
+// dtw of one cost matrix [N][M] -> trace [(N + 1)][(M + 1)].  N <= DTW_OPEN_MAX_ROWS (below), as for every dtw launcher here:
+// more rows are refused with hipErrorInvalidValue (n_text_ctx is 448)
 hipError_t launch_dtw(const float* x, int N, int M, int8_t* trace, hipStream_t stream);
 // batched find_alignment post-processing: clip b has ntok[b] token rows and nfr[b] frames (device arrays) inside slabs
 // qk [clips][H][Tmax][Tk]; cost [clips][Nmax][Fmax] = -mean over heads of rows [row_begin, ntok[b] - row_tail);
@@ -395,14 +397,16 @@ hipError_t launch_dtw(const float* x, int N, int M, int8_t* trace, hipStream_t s
 hipError_t launch_align_batch(const float* qk, const int* d_ntok, const int* d_nfr, int clips, int H, int Tmax, int Tk,
                               int Fmax, int width, int row_begin, int row_tail, float qk_scale, float* cost, int Nmax,
                               float* scratch, hipStream_t stream);
-// dtw of every clip's cost matrix; trace of clip b dense [(N_b + 1)][(F_b + 1)] at trace + b * trace_bs
+// dtw of every clip's cost matrix; trace of clip b dense [(N_b + 1)][(F_b + 1)] at trace + b * trace_bs.
+// Nmax <= DTW_OPEN_MAX_ROWS (below)
 hipError_t launch_dtw_batch(const float* cost, const int* d_ntok, const int* d_nfr, int clips, int Tmax, int Fmax,
                             int row_begin, int row_tail, int Nmax, int8_t* trace, int64_t trace_bs, hipStream_t stream);
 // open-end dtw: clip b's cost matrix [d_rows[b]][d_cols[b]] (row stride Fmax, slab of Nmax rows); trace as launch_dtw_batch
 // (trace_bs >= (Nmax + 1) * (Fmax + 1)); lastcol [clips][Nmax] = accumulated cost of the last column; end [clips] = the row the
 // path leaves the window at: d_rows[b] where d_closed[b] != 0, else the smallest i with lastcol[i-1] <= m + end_slack * |m|,
 // m the column's minimum; 0 for an empty clip.  Pass `end` to launch_dtw_backtrace_batch as its row counts.
-// Nmax <= DTW_OPEN_MAX_ROWS: the wavefront keeps three diagonals of Nmax + 1 floats in 64 KB of LDS.
+// Nmax <= DTW_OPEN_MAX_ROWS: the wavefront keeps three diagonals of Nmax + 1 floats in 64 KB of LDS.  The same limit holds
+// for launch_dtw and launch_dtw_batch (the same wavefront, the same LDS, no raise_dynamic_lds).
 constexpr int DTW_OPEN_MAX_ROWS = 5460;
 hipError_t launch_dtw_open_batch(const float* cost, const int* d_rows, const int* d_cols, const int* d_closed, int clips,
                                  int Nmax, int Fmax, float end_slack, int8_t* trace, int64_t trace_bs, float* lastcol,

@@ -293,6 +293,63 @@ int wht_dtw_open(const float* cost, const int* d_rows, const int* d_cols, const 
                                     path_len, (hipStream_t)stream);
 }
 
+// generic attention (decoder prefill, non-flash cross attention, the fp32 encoder): every AttnArgs field as given
+int wht_attn_generic(int dtype, int batch, const void* q, int64_t q_ld, int64_t q_bs, const void* k, int64_t k_ld, int64_t k_bs,
+                     const void* v, int64_t v_ld, int64_t v_bs, void* out, int64_t o_ld, int64_t o_bs, int H, int Tq, int Tk,
+                     const int* d_len, int causal, int kv_group, void* stream) {
+  AttnArgs a;
+  memset(&a, 0, sizeof a);
+  a.q = q; a.q_ld = q_ld; a.q_bs = q_bs; a.k = k; a.k_ld = k_ld; a.k_bs = k_bs; a.v = v; a.v_ld = v_ld; a.v_bs = v_bs;
+  a.out = out; a.o_ld = o_ld; a.o_bs = o_bs; a.H = H; a.Tq = Tq; a.Tk = Tk; a.d_len = d_len; a.causal = causal;
+  a.kv_group = kv_group;
+  return launch_attn_generic(a, batch, dtype, (hipStream_t)stream);
+}
+
+// the word-timestamp score planes: one (q, k, head), and every (row, pair) plane of a batch
+int wht_cross_qk(const void* q, int64_t q_ld, const void* k, int64_t k_ld, int head, int n_tok, int Tk, float* out, int dtype,
+                 void* stream) {
+  return launch_cross_qk(q, q_ld, k, k_ld, head, n_tok, Tk, out, dtype, (hipStream_t)stream);
+}
+int wht_cross_qk_batch(const void* qcap, int64_t q_layer_stride, int64_t q_row_stride, int D, const void* cross_kv,
+                       int64_t kv_layer_stride, int64_t kv_audio_stride, int kv_group, const int* d_layers, const int* d_heads,
+                       int n_pairs, const int* d_ntok, int R, int Tmax, int Tk, float* out, int dtype, void* stream) {
+  return launch_cross_qk_batch(qcap, q_layer_stride, q_row_stride, D, cross_kv, kv_layer_stride, kv_audio_stride, kv_group,
+                               d_layers, d_heads, n_pairs, d_ntok, R, Tmax, Tk, out, dtype, (hipStream_t)stream);
+}
+
+// the alignment pipeline on a caller-owned scratch of 2 * clips * H * Tmax * Fmax floats: afterwards its first half holds
+// softmax + z-norm, its second half the median
+int wht_align_batch(const float* qk, const int* d_ntok, const int* d_nfr, int clips, int H, int Tmax, int Tk, int Fmax,
+                    int width, int row_begin, int row_tail, float qk_scale, float* cost, int Nmax, float* scratch,
+                    void* stream) {
+  return launch_align_batch(qk, d_ntok, d_nfr, clips, H, Tmax, Tk, Fmax, width, row_begin, row_tail, qk_scale, cost, Nmax,
+                            scratch, (hipStream_t)stream);
+}
+int wht_dtw(const float* x, int N, int M, int8_t* trace, void* stream) { return launch_dtw(x, N, M, trace, (hipStream_t)stream); }
+int wht_dtw_batch(const float* cost, const int* d_ntok, const int* d_nfr, int clips, int Tmax, int Fmax, int row_begin,
+                  int row_tail, int Nmax, int8_t* trace, int64_t trace_bs, void* stream) {
+  return launch_dtw_batch(cost, d_ntok, d_nfr, clips, Tmax, Fmax, row_begin, row_tail, Nmax, trace, trace_bs,
+                          (hipStream_t)stream);
+}
+
+// the small kernels around the encoder stem, the prefill and the sampler
+int wht_mel_transpose(const void* mel, int mel_is_f16, int B, int n_mels, int F, void* out, int dtype, void* stream) {
+  return launch_mel_transpose(mel, mel_is_f16, B, n_mels, F, out, dtype, (hipStream_t)stream);
+}
+int wht_embed(const int64_t* tokens, int64_t stride, int R, int T0, const void* tok_emb, const float* pos, const int* d_offset,
+              const int* lag, int D, int n_vocab, float* x, int dtype, void* stream) {
+  return launch_embed(tokens, stride, R, T0, tok_emb, pos, d_offset, lag, D, n_vocab, x, dtype, (hipStream_t)stream);
+}
+int wht_no_speech(const float* logits_row0, int64_t row_stride, int R, int V, int no_speech, float* out, void* stream) {
+  return launch_no_speech(logits_row0, row_stride, R, V, no_speech, out, (hipStream_t)stream);
+}
+int wht_gather_rows(const float* x, const int* sel, int n_sel, int D, float* out, void* stream) {
+  return launch_gather_rows(x, sel, n_sel, D, out, (hipStream_t)stream);
+}
+int wht_gather_tokens(const int64_t* src, int64_t stride, int R, int64_t* dst, void* stream) {
+  return launch_gather_tokens(src, stride, R, dst, (hipStream_t)stream);
+}
+
 // flac.hip, stage by stage on a caller-supplied scratch (flac_scratch layout, >= wht_flac_scratch_bytes).  wht_flac_scan: the
 // candidate list of file[first, size) -> host n_found [1] (all candidates; the list holds min(n_found, max_cand)), start / bs /
 // prov [max_cand].  wht_flac_decode (after wht_flac_scan on the same scratch): every listed candidate decoded into pcm

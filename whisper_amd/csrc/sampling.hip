@@ -479,7 +479,8 @@ __global__ __launch_bounds__(1024) void no_speech_kernel(const float* __restrict
 #pragma unroll
     for (int j = 0; j < UN; ++j) {
       if (v0 + j * 1024 + tid < V) {
-        if (xv[j] > m) { s = s * expf(m - xv[j]) + 1.0f; m = xv[j]; } else s += expf(xv[j] - m);
+        // a -inf logit adds nothing; while m is still -inf, expf(-inf - m) would be expf(NaN)
+        if (xv[j] > m) { s = s * expf(m - xv[j]) + 1.0f; m = xv[j]; } else if (xv[j] != WH_NEG_INF) s += expf(xv[j] - m);
       }
     }
   }

@@ -446,7 +446,8 @@ hipError_t launch_align_matrix(const float* qk, int H, int T, int Tk, int F, int
 
 hipError_t launch_dtw_batch(const float* cost, const int* d_ntok, const int* d_nfr, int clips, int Tmax, int Fmax,
                             int row_begin, int row_tail, int Nmax, int8_t* trace, int64_t trace_bs, hipStream_t stream) {
-  if (Nmax <= 0 || Nmax > 8192) return hipErrorInvalidValue;
+  // three diagonals of Nmax + 1 floats in the 64 KB of dynamic LDS a kernel gets without asking for more
+  if (Nmax <= 0 || Nmax > DTW_OPEN_MAX_ROWS) return hipErrorInvalidValue;
   AlignBatch ab; ab.ntok = d_ntok; ab.nfr = d_nfr; ab.H = 0; ab.Tmax = Tmax; ab.Tk = 0; ab.Fmax = Fmax;
   int threads = ((Nmax + 63) / 64) * 64;
   if (threads > 1024) threads = 1024;
@@ -509,7 +510,7 @@ hipError_t launch_median_filter(const float* x, float* out, int64_t rows, int n,
 }
 
 hipError_t launch_dtw(const float* x, int N, int M, int8_t* trace, hipStream_t stream) {
-  if (N <= 0 || M <= 0 || N > 8192) return hipErrorInvalidValue;
+  if (N <= 0 || M <= 0 || N > DTW_OPEN_MAX_ROWS) return hipErrorInvalidValue;   // 3 x (N + 1) floats of LDS, as launch_dtw_batch
   int threads = ((N + 63) / 64) * 64;
   if (threads > 1024) threads = 1024;
   const size_t lds = 3 * (size_t)(N + 1) * sizeof(float);
