@@ -382,7 +382,9 @@ typedef struct wh_greedy_params {
   const uint8_t *suppress_mask;  /* device [n_vocab] bytes: 1 = token in SuppressTokens list */
   float temperature;             /* 0: arg-max (decoding.py:278-279); > 0: Categorical(logits / temperature).sample()
                                     (:281-283) drawn on the device by Gumbel-max with counter-based noise — the same
-                                    distribution, not torch's random stream; wh_task_greedy only */
+                                    distribution, not torch's random stream; wh_task_greedy only.  The noise of an entry
+                                    is -log(-log u), u a 23-bit uniform in [2^-24, 1 - 2^-24] hashed from (seed, step,
+                                    row, token): finite, about [-2.81, 16.64] */
   uint32_t reserved;
   uint64_t seed;                 /* noise key of this call (temperature > 0) */
 } wh_greedy_params;

@@ -52,6 +52,12 @@ SIGNATURES = {
     "wht_no_speech": (_I, [_P, _L, _I, _I, _I, _P, _P]),
     "wht_gather_rows": (_I, [_P, _P, _I, _I, _P, _P]),
     "wht_gather_tokens": (_I, [_P, _L, _I, _P, _P]),
+    # the sampler's noise on the host (sample_noise.h): nothing is launched, no GPU is needed
+    "wht_sample_hash": (ctypes.c_uint32, [ctypes.c_uint64, _I, _I, _I]),
+    "wht_sample_uniform_of_hash": (ctypes.c_float, [ctypes.c_uint32]),
+    "wht_sample_uniform_bits": (_I, []),
+    "wht_sample_uniform_range": (None, [ctypes.c_uint32, ctypes.c_uint32, _P]),
+    "wht_sample_hash_many": (None, [_P, _P, _P, _P, _L, _P]),
 }
 
 _lib = None

@@ -49,11 +49,13 @@ class Trie:
 
 
 def sampler_step(logits: np.ndarray, sampled: Sequence[int], state: int, trie: Trie, boost: float, r: SamplingRules,
-                 ended: bool = False):
+                 ended: bool = False, info: Optional[dict] = None):
     """One row, one step, in float64: bias -> SuppressBlank -> SuppressTokens -> ApplyTimestampRules -> arg-max (lowest id
     among equal maxima) -> log_softmax of the filtered row.  `sampled`: the row's sampled tokens so far; the state counts
     as the root when there are none.  `ended`: the row's last token is <|endoftext|> (it stays there, nothing is
-    accumulated).  Returns (token, log-probability to accumulate or None, new state, filtered float64 row)."""
+    accumulated).  Returns (token, log-probability to accumulate or None, new state, filtered float64 row).
+    `info`: a dict that receives, where the timestamp rules are on, the two sides of the timestamp-mass rule (ts_lse,
+    text_max) with ts_max and the log-sum-exp of the whole row, all taken before the rule is applied."""
     x = np.asarray(logits, dtype=np.float64).copy()
     if len(sampled) == 0:
         state = 0
@@ -88,6 +90,9 @@ def sampler_step(logits: np.ndarray, sampled: Sequence[int], state: int, trie: T
         def lse(v):
             m = v.max() if v.size else -np.inf
             return -np.inf if m == -np.inf else m + math.log(np.exp(v - m).sum())
+        if info is not None:                      # the two sides of the mass rule, before it is applied
+            info.update(ts_lse=lse(x[TB:]), ts_max=x[TB:].max() if x[TB:].size else -np.inf,
+                        text_max=x[:TB].max() if TB > 0 else -np.inf, all_lse=lse(x))
         if lse(x[TB:]) > (x[:TB].max() if TB > 0 else -np.inf):      # the same normaliser on both sides
             x[:TB] = -np.inf
     m = x.max()

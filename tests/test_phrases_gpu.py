@@ -254,10 +254,11 @@ def test_sampler_kernels_against_float64(gpu_device, V, R, mode):
 
 
 def test_sampling_instantiation_draws_the_forced_token(gpu_device):
-    """<true, true>: temperature 1, boost 48 on a one-phrase list.  The 24-bit uniform lies in [2^-25, 1 - 2^-25], so the
-    Gumbel noise -log(-log u) lies in [-2.86, 17.33]: a range of 20.2; the logits are drawn with |x| < 12: a range of 24;
-    48 / T = 48 > 44.2, so the boosted token's key exceeds every other key whatever the noise and it is drawn with
-    certainty.  Its log-probability is the unscaled x + 48 - log-sum-exp of the biased row."""
+    """<true, true>: temperature 1, boost 48 on a one-phrase list.  The 23-bit uniform lies in [2^-24, 1 - 2^-24]
+    (sample_noise.h), so the Gumbel noise -log(-log u) lies in [-2.81, 16.64]: a range of 19.5, for which 20.2 (17.33 + 2.86
+    below) is an upper bound; the logits are drawn with |x| < 12: a range of 24; 48 / T = 48 > 44.2, so the boosted token's
+    key exceeds every other key whatever the noise and it is drawn with certainty.  Its log-probability is the unscaled
+    x + 48 - log-sum-exp of the biased row."""
     V, R, a = 51866, 24, 1234
     rng = np.random.default_rng(5)
     trie = phrase_oracle.Trie([[a]])

@@ -248,8 +248,8 @@ def test_sampler_kernels_against_float64(gpu_device, V, R, mode):
 
 
 def test_sampling_instantiation_never_draws_the_banned_token(gpu_device):
-    """<true, false, true>: temperature 1.  The Gumbel noise of the 24-bit uniform spans 20.2 (test_phrases_gpu.py) and the
-    logits are drawn with |x| < 12, a spread of 24.  Token a sits 48 > 20.2 above token b and b 48 > 20.2 + 24 above
+    """<true, false, true>: temperature 1.  The Gumbel noise of the 23-bit uniform lies in [-2.81, 16.64] and spans less than
+    20.2 (test_phrases_gpu.py) and the logits are drawn with |x| < 12, a spread of 24.  Token a sits 48 > 20.2 above token b and b 48 > 20.2 + 24 above
     everything else: without the ban a is drawn with certainty, with it (n = 1, a sampled before) a is never drawn and b
     is, with certainty.  Its log-probability is x[b] - log-sum-exp of the EDITED row (a at -inf)."""
     V, R, a, b_ = 51866, 24, 1234, 4321

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "kernels.h"
+#include "sample_noise.h"
 
 using namespace whk;
 
@@ -204,6 +205,20 @@ int wht_greedy_sample_rep(const float* logits, int64_t logits_ld, int R, int V, 
   return launch_greedy_sample(a, (hipStream_t)stream, &ph, &rep);
 }
 size_t wht_greedy_sample_scratch_bytes(int R, int V) { return greedy_sample_scratch_bytes(R, V); }
+// the sampler's noise (sample_noise.h) on the host; nothing is launched.  wht_sample_uniform_range: the uniforms of `count`
+// consecutive values, from `first`, of the wht_sample_uniform_bits() top bits of a hash that the map uses
+uint32_t wht_sample_hash(uint64_t seed, int step, int row, int token) {
+  return sample_hash((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), step, row, token);
+}
+float wht_sample_uniform_of_hash(uint32_t h) { return sample_uniform_of_hash(h); }
+int wht_sample_uniform_bits() { return SAMPLE_UNIFORM_BITS; }
+void wht_sample_uniform_range(uint32_t first, uint32_t count, float* out) {
+  for (uint32_t i = 0; i < count; ++i) out[i] = sample_uniform_of_hash((first + i) << (32 - SAMPLE_UNIFORM_BITS));
+}
+// the hashes of `count` (seed, step, row, token) tuples in one call
+void wht_sample_hash_many(const uint64_t* seed, const int* step, const int* row, const int* token, int64_t count, uint32_t* out) {
+  for (int64_t i = 0; i < count; ++i) out[i] = wht_sample_hash(seed[i], step[i], row[i], token[i]);
+}
 int wht_phrase_root_table(const int* child_begin, const int* child_token, const int* child_node, int n_edges, int V, int* root,
                           void* stream) {
   return launch_phrase_root_table(child_begin, child_token, child_node, n_edges, V, root, (hipStream_t)stream);

@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "sample_noise.h"
 
 namespace {
 
@@ -65,16 +66,10 @@ __device__ __forceinline__ void pick_wave_reduce(Pick& a) {
     pick_merge(a, key, x, idx);
   }
 }
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-// standard Gumbel noise for (seed, step, row, token); 24-bit uniform strictly inside (0, 1)
+// standard Gumbel noise for (seed, step, row, token): hash and uniform of sample_noise.h.  The 23-bit uniform lies in
+// [2^-24, 1 - 2^-24], strictly inside (0, 1) in fp32, so the noise is finite: about [-2.81, 16.64]
 __device__ __forceinline__ float gumbel(uint32_t seed_lo, uint32_t seed_hi, int step, int row, int v) {
-  uint32_t h = fmix32((uint32_t)row * 0x9E3779B1u + (uint32_t)step) ^ seed_lo;
-  h = fmix32(h ^ (uint32_t)v * 0x85EBCA77u);
-  h = fmix32(h + seed_hi);
-  const float u = ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u = sample_uniform_of_hash(sample_hash(seed_lo, seed_hi, step, row, v));
   return -logf(-logf(u));
 }
 constexpr int PSTRIDE = 8;      // floats per (row, chunk, range) partial: m, s, idx | key, x (sampling)
