@@ -58,6 +58,7 @@ SIGNATURES = {
     "wht_sample_uniform_bits": (_I, []),
     "wht_sample_uniform_range": (None, [ctypes.c_uint32, ctypes.c_uint32, _P]),
     "wht_sample_hash_many": (None, [_P, _P, _P, _P, _L, _P]),
+    "wht_rule_mask": (None, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

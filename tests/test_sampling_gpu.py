@@ -288,6 +288,41 @@ def test_every_entry_filtered(gpu_device):
     _static_untouched(fam, st)
 
 
+def test_timestamp_rules_need_the_row_state(gpu_device):
+    """wht_greedy_sample with timestamp rules on and no row_state: hipErrorInvalidValue and every buffer as it was (the
+    partial kernel takes the rules' window from the state alone).  R = 1, V = 1025: two vocabulary chunks, the second of one
+    entry.  The same call with the rules off (timestamp_begin = -1) is accepted."""
+    h = tp.klib()
+    V, T0, stride = 1025, 3, 6
+    x = np.random.default_rng(5).standard_normal((1, V)).astype(np.float32)
+    tokens = np.full((1, stride), -7, dtype=np.int64)
+    tokens[0, :T0] = 50258
+    nbytes = h.wht_greedy_sample_scratch_bytes(1, V)
+    b = dict(x=Buf(x), mask=Buf(np.zeros(V, np.uint8)), tokens=Buf(tokens), ntok=Buf(np.array([T0], np.int32)),
+             sums=Buf(np.array([-1.5], np.float32)), step=Buf(np.full(1, -7, np.int64)), alive=Buf(np.array([-5], np.int32)),
+             part=Buf(np.zeros(nbytes // 4, np.float32)))
+    before = {k: v.get() for k, v in b.items()}
+
+    def call(TB):
+        rc = h.wht_greedy_sample(b["x"].ptr(), V, 1, V, b["tokens"].ptr(), stride, b["ntok"].ptr(), None, T0, 1000, TB, 1001, 5, 1,
+                                 220, b["mask"].ptr(), b["sums"].ptr(), b["step"].ptr(), b["alive"].ptr(), b["part"].ptr(), nbytes,
+                                 0.0, 0, None, 0, 0, None, None, None, None, None, 0.0, None)
+        torch.cuda.synchronize()
+        for name, buf in b.items():
+            assert buf.guards_intact(), name
+        return rc
+
+    assert call(1002) == tp.kernel_lib.hipErrorInvalidValue
+    for name, buf in b.items():
+        assert np.array_equal(buf.get().view(np.uint8), before[name].view(np.uint8)), f"{name} was written"
+    assert call(-1) == 0
+    out = {k: v.get() for k, v in b.items()}
+    want = np.where((np.arange(V) == 220) | (np.arange(V) == 1000), -np.inf, x[0].astype(np.float64))     # SuppressBlank at L = 0
+    assert out["tokens"][0, T0] == out["step"][0] == int(np.argmax(want)) and out["alive"][0] == T0
+    assert np.array_equal(out["tokens"][0, :T0], tokens[0, :T0]) and np.array_equal(out["tokens"][0, T0 + 1:], tokens[0, T0 + 1:])
+    assert np.array_equal(out["x"].view(np.uint32), x.view(np.uint32))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. the loop's plumbing: seed words, step counter, row numbering
 # ---------------------------------------------------------------------------------------------------------------------

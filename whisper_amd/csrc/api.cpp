@@ -1268,9 +1268,8 @@ static int replicate_leader_rows(wh_task* t, int T0, float* logits, int n_sel, h
   return WH_OK;
 }
 
-// the rows and sampling rules the greedy sampler and the beam update share (SampleArgs / BeamArgs name them alike)
-template <class Args>
-static void set_sampling_rules(Args& a, const wh_task* t, const wh_loop* L) {
+// the rows and sampling rules the greedy sampler and the beam update share
+static void set_sampling_rules(RuleArgs& a, const wh_task* t, const wh_loop* L) {
   const wh_greedy_params* p = &L->bp.rules;
   a.R = t->R; a.V = t->m->d.n_vocab; a.token_stride = L->token_stride; a.d_ntok = t->d_pos; a.lag = t->d_lag;
   a.sample_begin = p->sample_begin; a.eot = p->eot; a.timestamp_begin = p->timestamp_begin; a.no_timestamps = p->no_timestamps;
@@ -1316,7 +1315,7 @@ static int greedy_start(wh_task* t) {
   HIPCHK(hipMemcpyAsync(t->d_alive, hp + HP_ALIVE_INIT, 4, hipMemcpyHostToDevice, s));
 
   SampleArgs& sa = L->sa; memset(&sa, 0, sizeof(sa));
-  set_sampling_rules(sa, t, L);
+  set_sampling_rules(sa.rules, t, L);
   sa.tokens = L->tokens;
   sa.step_tokens = t->step_tokens; sa.d_alive_step = t->d_alive; sa.partials = t->samp_part;
   sa.row_state = t->samp_state;
@@ -1340,9 +1339,9 @@ static int greedy_start(wh_task* t) {
     sa.inv_temperature = 1.0f / p->temperature;
     sa.seed_lo = (uint32_t)(p->seed & 0xffffffffu); sa.seed_hi = (uint32_t)(p->seed >> 32);
   }
-  sa.logits = t->logits + (size_t)(n_sel - 1) * V; sa.logits_ld = (int64_t)n_sel * V;
+  sa.rules.logits = t->logits + (size_t)(n_sel - 1) * V; sa.rules.logits_ld = (int64_t)n_sel * V;
   HIPCHK(launch_greedy_sample(sa, s, L->biased ? &ph : nullptr, L->rep_on ? &L->rep : nullptr));
-  sa.logits = t->logits; sa.logits_ld = V;
+  sa.rules.logits = t->logits; sa.rules.logits_ld = V;
   L->ntok = T0 + 1; L->steps = 1;
   L->pending = L->wait_due = false; L->ntok_at_copy = 0;
   L->phase = PH_STEPPING;
@@ -1360,7 +1359,7 @@ static int beam_update(wh_task* t, const float* logits, int64_t logits_ld, int f
   int64_t* buf[2] = {L->tokens, L->tokens + (int64_t)R * L->token_stride};
   int* done[2] = {t->beam_flags, t->beam_flags + B};
   BeamArgs& a = L->ba;
-  a.logits = logits; a.logits_ld = logits_ld; a.first = first;
+  a.rules.logits = logits; a.rules.logits_ld = logits_ld; a.first = first;
   a.tokens_in = buf[L->cur]; a.tokens_out = buf[L->cur ^ 1];
   a.done_prev = done[L->cur]; a.done_next = done[L->cur ^ 1];
   HIPCHK(launch_beam_step(a, B, L->s));
@@ -1387,7 +1386,7 @@ static int beam_start(wh_task* t) {
   HIPCHK(hipMemsetAsync(t->beam_flags, 0, (2 * (size_t)B + 1) * 4, s));
 
   BeamArgs& a = L->ba; memset(&a, 0, sizeof(a));
-  set_sampling_rules(a, t, L);
+  set_sampling_rules(a.rules, t, L);
   a.G = G; a.K = G + 1;
   beam_scratch_carve(a, t->beam_scratch, R, V);
   a.fin_tok = L->fin_tokens; a.fin_len = L->fin_len; a.fin_score = L->fin_scores; a.fin_count = L->fin_count;

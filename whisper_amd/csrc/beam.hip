@@ -1,11 +1,10 @@
 // beam.hip — the logits epilogue and candidate bookkeeping of beam search, on the device:
-//   DecodingTask._main_loop (whisper/decoding.py:696-703) with BeamSearchDecoder.update (:323-382) and the
-//   SuppressBlank / SuppressTokens / ApplyTimestampRules filters (:423-505).
+//   DecodingTask._main_loop (whisper/decoding.py:696-703) with BeamSearchDecoder.update (:323-382) and the stock logit
+//   rules (logit_rules.h).
 // Three kernels per step, no host synchronisation:
 //   beam_partial_kernel  grid (vocabulary chunks, rows): filters one 1024-entry slice of a row and reduces it to online
 //                        softmax statistics and its K = beam + 1 best entries, separately for the text range
-//                        [0, timestamp_begin) and the timestamp range (the "timestamp mass" rule :498-505 decides
-//                        later whether text is allowed at all);
+//                        and the timestamp range (the timestamp mass rule decides later whether text is allowed at all);
 //   beam_row_kernel      grid (rows): merges the chunk partials -> log_softmax normaliser of the filtered row and its
 //                        top K (log-probability, token) pairs == F.log_softmax(logits).topk(beam + 1) (:333-345);
 //   beam_update_kernel   grid (audio segments): the candidate bookkeeping of one segment — scores = sum_logprobs + logprob
@@ -22,35 +21,15 @@
 // everything untouched until the host polls them.
 #include "common.h"
 #include "kernels.h"
+#include "logit_rules.h"
 
 namespace {
 
+using namespace whk;
+
 constexpr int BCHUNK = 1024;     // vocabulary entries per partial workgroup (256 threads x 4)
 constexpr int KMAX = whk::BEAM_KMAX;
-constexpr int NO_IDX = 0x7fffffff;
-
-struct Stat {           // online softmax statistics of a range
-  float m, s;
-};
-__device__ __forceinline__ void stat_add(Stat& a, float x) {
-  if (x == WH_NEG_INF) return;
-  if (x > a.m) { a.s = a.s * expf(a.m - x) + 1.0f; a.m = x; }
-  else { a.s += expf(x - a.m); }
-}
-__device__ __forceinline__ void stat_merge(Stat& a, float m, float s) {
-  if (m == WH_NEG_INF) return;
-  if (a.m == WH_NEG_INF) { a.m = m; a.s = s; return; }
-  if (m > a.m) { a.s = a.s * expf(a.m - m) + s; a.m = m; }
-  else { a.s += s * expf(m - a.m); }
-}
-__device__ __forceinline__ void stat_wave_reduce(Stat& a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m = __shfl_xor(a.m, o, 64);
-    const float s = __shfl_xor(a.s, o, 64);
-    stat_merge(a, m, s);
-  }
-}
+typedef Stat<false> BStat;       // the top K come from the selection below: no arg-max index in the statistics
 
 // larger value wins; equal values: smaller index wins
 __device__ __forceinline__ void best_merge(float& v, int& i, float v2, int i2) {
@@ -77,92 +56,43 @@ __global__ __launch_bounds__(256) void beam_partial_kernel(whk::BeamArgs a, int 
   pin_kernargs(a);
   asm volatile("" ::"s"(nchunk));      // == gridDim.x, as an argument: gridDim sits in the implicit arguments
   __shared__ int sh_last_ts;
-  __shared__ float sh_m[2][4], sh_s[2][4];
+  __shared__ BlockStats<false> sh_st;
   __shared__ float sh_bv[4];
   __shared__ int sh_bi[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const RuleArgs& r = a.rules;
+  const int tid = threadIdx.x;
   const int c = blockIdx.x, k = blockIdx.y;
-  const float* x = a.logits + (int64_t)k * a.logits_ld;
+  const float* x = r.logits + (int64_t)k * r.logits_ld;
   float xv[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int v = c * BCHUNK + j * 256 + tid;
-    xv[j] = v < a.V ? x[v] : WH_NEG_INF;
+    xv[j] = v < r.V ? x[v] : WH_NEG_INF;
   }
-  const int lag = a.lag ? a.lag[k] : 0;                   // ragged prompts: this row's sequence is `lag` tokens shorter
-  const int ntok = load_uniform_int(a.d_ntok) - lag;
-  const int sample_begin = a.sample_begin - lag;
-  const int64_t* row = a.tokens_in + (int64_t)k * a.token_stride;
-  const int L = ntok - sample_begin;
-  const int TB = a.timestamp_begin;       // < 0: timestamp rules disabled (without_timestamps)
-  const bool ts_rules = TB >= 0;
+  const RowPos pos = row_pos(r, k);
+  // a beam's history changes hands at every update (another source row): the window is read off the row's tokens
+  const TsWindow win = ts_window_scan(r, pos, a.tokens_in + (int64_t)k * r.token_stride, &sh_last_ts);
+  const int split = r.timestamp_begin >= 0 ? r.timestamp_begin : r.V;   // text range [0, split), timestamp range [split, V)
 
-  if (tid == 0) sh_last_ts = -1;
-  __syncthreads();
-  if (ts_rules) {
-    for (int t = tid; t < L; t += 256)
-      if (row[sample_begin + t] >= TB) atomicMax(&sh_last_ts, t);
-  }
-  __syncthreads();
-
-  bool last_ts = false, pen_ts = false;
-  int ts_lo = 0, ts_hi = 0;              // forbidden timestamp interval [ts_lo, ts_hi)
-  if (ts_rules) {
-    last_ts = (L >= 1) && (row[ntok - 1] >= TB);
-    pen_ts = (L < 2) || (row[ntok - 2] >= TB);
-    if (sh_last_ts >= 0) {
-      const int t = (int)row[sample_begin + sh_last_ts];
-      ts_lo = TB;
-      ts_hi = (last_ts && !pen_ts) ? t : t + 1;
-    }
-  }
-  const int split = ts_rules ? TB : a.V;   // text range [0, split), timestamp range [split, V)
-
-  Stat st[2];
-  st[0] = Stat{WH_NEG_INF, 0.f};
-  st[1] = Stat{WH_NEG_INF, 0.f};
-  unsigned live = 0;                       // bit j: entry j of this thread passes the filters
+  BStat st[2];
+  unsigned live = 0;                       // bit j: entry j of this thread passes the filters (logit_rules.h: rule_masked)
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int v = c * BCHUNK + j * 256 + tid;
-    bool masked = v >= a.V;
-    if (!masked) {
-      masked = a.suppress_mask && a.suppress_mask[v];
-      if (a.suppress_blank && L == 0 && (v == a.blank_token || v == a.eot)) masked = true;
-      if (ts_rules) {
-        if (v == a.no_timestamps) masked = true;
-        if (last_ts) {
-          if (pen_ts) { if (v >= TB) masked = true; }
-          else { if (v < a.eot) masked = true; }
-        }
-        if (v >= ts_lo && v < ts_hi) masked = true;
-        if (L == 0) {
-          if (v < TB) masked = true;
-          if (a.max_initial_ts >= 0 && v > TB + a.max_initial_ts) masked = true;
-        }
-      }
-    }
-    // the survivors are tracked in a bit mask and selected at every use: a conditional `xv[j] = -inf` into the
-    // register array was dropped by the compiler here (empty if-body in the ISA; every filter silently off)
+    const bool masked = v >= r.V || rule_masked(r, pos, win, v);
     live |= (masked ? 0u : 1u) << j;
-    if (!masked) { if (v < split) stat_add(st[0], xv[j]); else stat_add(st[1], xv[j]); }
+    if (!masked) { if (v < split) stat_add(st[0], xv[j], v); else stat_add(st[1], xv[j], v); }
   }
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    stat_wave_reduce(st[g]);
-    if (lane == 0) { sh_m[g][wave] = st[g].m; sh_s[g][wave] = st[g].s; }
-  }
-  __syncthreads();
+  sh_st.reduce(st);
   if (tid < 2) {
-    Stat t = Stat{WH_NEG_INF, 0.f};
-    for (int w = 0; w < 4; ++w) stat_merge(t, sh_m[tid][w], sh_s[tid][w]);
+    const BStat t = sh_st.range(tid);
     float* o = a.part_stat + (((int64_t)k * nchunk + c) * 2 + tid) * 2;
     o[0] = t.m; o[1] = t.s;
   }
 
   // the K best entries of the slice, per range
   const int K = a.K;
-  const int lo = c * BCHUNK, hi = (lo + BCHUNK < a.V) ? lo + BCHUNK : a.V;
+  const int lo = c * BCHUNK, hi = (lo + BCHUNK < r.V) ? lo + BCHUNK : r.V;
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
     float* pv = a.part_val + (((int64_t)k * nchunk + c) * 2 + g) * KMAX;
@@ -198,24 +128,22 @@ constexpr int POOL_MAX = 2 * 64 * KMAX;     // both ranges x up to 64 chunks x K
 __global__ __launch_bounds__(256) void beam_row_kernel(whk::BeamArgs a, int nchunk) {
   pin_kernargs(a);
   asm volatile("" ::"s"(nchunk));
-  __shared__ float sh_m[2][4], sh_s[2][4];
+  __shared__ BlockStats<false> sh_st;
   __shared__ float sh_bv[4];
   __shared__ int sh_bi[4];
   __shared__ float pool_v[POOL_MAX];
   __shared__ int pool_i[POOL_MAX];
   __shared__ int sh_text_masked;
   __shared__ float sh_norm[2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int k = blockIdx.x;
-  const bool ts_rules = a.timestamp_begin >= 0;
-  Stat st[2];
-  st[0] = Stat{WH_NEG_INF, 0.f};
-  st[1] = Stat{WH_NEG_INF, 0.f};
+  const bool ts_rules = a.rules.timestamp_begin >= 0;
+  BStat st[2];
   for (int c = tid; c < nchunk; c += 256) {
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       const float* o = a.part_stat + (((int64_t)k * nchunk + c) * 2 + g) * 2;
-      stat_merge(st[g], o[0], o[1]);
+      stat_merge(st[g], BStat{o[0], o[1]});
     }
   }
   const int K = a.K;
@@ -225,33 +153,10 @@ __global__ __launch_bounds__(256) void beam_row_kernel(whk::BeamArgs a, int nchu
     pool_v[e] = a.part_val[((int64_t)k * nchunk * 2 + cg) * KMAX + kk];
     pool_i[e] = a.part_idx[((int64_t)k * nchunk * 2 + cg) * KMAX + kk];
   }
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    stat_wave_reduce(st[g]);
-    if (lane == 0) { sh_m[g][wave] = st[g].m; sh_s[g][wave] = st[g].s; }
-  }
-  __syncthreads();
+  sh_st.reduce(st);
   if (tid == 0) {
-    Stat tx = Stat{WH_NEG_INF, 0.f}, ts = tx;
-    for (int w = 0; w < 4; ++w) {
-      stat_merge(tx, sh_m[0][w], sh_s[0][w]);
-      stat_merge(ts, sh_m[1][w], sh_s[1][w]);
-    }
-    bool text_masked = false;
-    if (ts_rules) {
-      // decoding.py:498-505 — logsumexp of timestamp logprobs vs max text logprob (same normaliser)
-      Stat all = tx;
-      stat_merge(all, ts.m, ts.s);
-      if (all.m != WH_NEG_INF) {
-        const float lse_all = logf(all.s);
-        const float ts_lp_max = (ts.m - all.m) - lse_all;
-        const float ts_lse = (ts.m == WH_NEG_INF) ? WH_NEG_INF : ts_lp_max + logf(ts.s);
-        const float text_lp_max = (tx.m == WH_NEG_INF) ? WH_NEG_INF : (tx.m - all.m) - lse_all;
-        if (ts_lse > text_lp_max) text_masked = true;
-      }
-    }
-    Stat fin = ts;
-    if (!text_masked) { fin = tx; stat_merge(fin, ts.m, ts.s); }
+    bool text_masked;
+    const BStat fin = allowed_range(sh_st.range(0), sh_st.range(1), ts_rules, &text_masked);
     sh_text_masked = text_masked ? 1 : 0;
     sh_norm[0] = fin.m;
     sh_norm[1] = (fin.m == WH_NEG_INF) ? 0.f : logf(fin.s);
@@ -295,7 +200,7 @@ __global__ __launch_bounds__(64) void beam_update_kernel(whk::BeamArgs a, int B)
   const int au = blockIdx.x;
   const int G = a.G, K = a.K;
   const int r0 = au * G;
-  const int len = load_uniform_int(a.d_ntok) - (a.lag ? a.lag[r0] : 0);    // the beams of a segment share its prompt
+  const int len = load_uniform_int(a.rules.d_ntok) - (a.rules.lag ? a.rules.lag[r0] : 0);    // the beams of a segment share its prompt
 
   // completed at the previous update (every segment full): leave the state as it is
   int not_done = 0;
@@ -305,8 +210,8 @@ __global__ __launch_bounds__(64) void beam_update_kernel(whk::BeamArgs a, int B)
   __syncthreads();
   if (sh_frozen) {
     for (int g = 0; g < G; ++g) {
-      const int64_t* s = a.tokens_in + (int64_t)(r0 + g) * a.token_stride;
-      int64_t* d = a.tokens_out + (int64_t)(r0 + g) * a.token_stride;
+      const int64_t* s = a.tokens_in + (int64_t)(r0 + g) * a.rules.token_stride;
+      int64_t* d = a.tokens_out + (int64_t)(r0 + g) * a.rules.token_stride;
       for (int t = tid; t < len; t += 64) d[t] = s[t];
       if (tid == 0) { a.src[r0 + g] = r0 + g; if (a.copy_from) a.copy_from[r0 + g] = 0; }
     }
@@ -320,7 +225,7 @@ __global__ __launch_bounds__(64) void beam_update_kernel(whk::BeamArgs a, int B)
     const int j = c / K, kk = c - j * K;
     const bool valid = a.first ? (j == G - 1) : true;
     const float lp = a.cand_lp[(int64_t)(r0 + j) * KMAX + kk];
-    score[c] = valid ? a.sum_logprobs[r0 + j] + lp : __builtin_nanf("");
+    score[c] = valid ? a.rules.sum_logprobs[r0 + j] + lp : __builtin_nanf("");
     ctok[c] = a.cand_tok[(int64_t)(r0 + j) * KMAX + kk];
     csrc[c] = r0 + j;
   }
@@ -346,7 +251,7 @@ __global__ __launch_bounds__(64) void beam_update_kernel(whk::BeamArgs a, int B)
     int kk = 0, nf = 0;
     for (int i = 0; i < nvalid && kk < G; ++i) {
       const int c = order[i];
-      if (ctok[c] == a.eot) nfin_list[nf++] = c;
+      if (ctok[c] == a.rules.eot) nfin_list[nf++] = c;
       else kept[kk++] = c;
     }
     sh_n[0] = nvalid; sh_n[1] = kk; sh_n[2] = nf;
@@ -357,11 +262,11 @@ __global__ __launch_bounds__(64) void beam_update_kernel(whk::BeamArgs a, int B)
   int count = a.fin_count[au];
   for (int i = 0; i < nf && count < a.max_candidates; ++i, ++count) {
     const int c = nfin_list[i];
-    const int64_t* s = a.tokens_in + (int64_t)csrc[c] * a.token_stride;
-    int64_t* d = a.fin_tok + ((int64_t)au * a.max_candidates + count) * a.token_stride;
+    const int64_t* s = a.tokens_in + (int64_t)csrc[c] * a.rules.token_stride;
+    int64_t* d = a.fin_tok + ((int64_t)au * a.max_candidates + count) * a.rules.token_stride;
     for (int t = tid; t < len; t += 64) d[t] = s[t];
     if (tid == 0) {
-      d[len] = a.eot;
+      d[len] = a.rules.eot;
       a.fin_len[au * a.max_candidates + count] = len + 1;
       a.fin_score[au * a.max_candidates + count] = score[c];
     }
@@ -369,8 +274,8 @@ __global__ __launch_bounds__(64) void beam_update_kernel(whk::BeamArgs a, int B)
   // the surviving beams
   for (int b = 0; b < nkept; ++b) {
     const int c = kept[b];
-    const int64_t* s = a.tokens_in + (int64_t)csrc[c] * a.token_stride;
-    int64_t* d = a.tokens_out + (int64_t)(r0 + b) * a.token_stride;
+    const int64_t* s = a.tokens_in + (int64_t)csrc[c] * a.rules.token_stride;
+    int64_t* d = a.tokens_out + (int64_t)(r0 + b) * a.rules.token_stride;
     for (int t = tid; t < len; t += 64) d[t] = s[t];
     if (tid == 0) {
       d[len] = ctok[c];
@@ -397,7 +302,7 @@ __global__ __launch_bounds__(64) void beam_update_kernel(whk::BeamArgs a, int B)
       a.copy_from[r0 + i] = cf;
     }
   }
-  if (tid < nkept) a.sum_logprobs[r0 + tid] = score[kept[tid]];
+  if (tid < nkept) a.rules.sum_logprobs[r0 + tid] = score[kept[tid]];
   if (tid == 0) {
     a.fin_count[au] = count;
     a.done_next[au] = count >= a.max_candidates ? 1 : 0;
@@ -426,10 +331,10 @@ void beam_scratch_carve(BeamArgs& a, void* base, int R, int V) {
 }
 
 hipError_t launch_beam_step(const BeamArgs& a, int B, hipStream_t stream) {
-  const int nchunk = (a.V + BCHUNK - 1) / BCHUNK;
-  if (a.K != a.G + 1 || a.K > KMAX || a.G > 8 || nchunk > 64 || a.R != B * a.G) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(beam_partial_kernel, dim3(nchunk, a.R), dim3(256), 0, stream, a, nchunk);
-  hipLaunchKernelGGL(beam_row_kernel, dim3(a.R), dim3(256), 0, stream, a, nchunk);
+  const int nchunk = (a.rules.V + BCHUNK - 1) / BCHUNK;
+  if (a.K != a.G + 1 || a.K > KMAX || a.G > 8 || nchunk > 64 || a.rules.R != B * a.G) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(beam_partial_kernel, dim3(nchunk, a.rules.R), dim3(256), 0, stream, a, nchunk);
+  hipLaunchKernelGGL(beam_row_kernel, dim3(a.rules.R), dim3(256), 0, stream, a, nchunk);
   hipLaunchKernelGGL(beam_update_kernel, dim3(B), dim3(64), 0, stream, a, B);
   return hipGetLastError();
 }

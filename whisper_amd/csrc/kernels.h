@@ -291,16 +291,23 @@ const char* gemv_family(const GemvArgs& a, int dtype);
 hipError_t launch_merge_partials(const void* part_o, const float* part_ml, int splits, int R, int H, void* out,
                                  int64_t o_ld, int dtype, hipStream_t stream, int o_frag = 0);
 
-// ---- sampling.hip --------------------------------------------------------------------------
-struct SampleArgs {
+// ---- logit_rules.h: what the greedy sampler and the beam update share -------------------------------------------------
+// the rows of a step and the stock logit rules (SuppressBlank, SuppressTokens, ApplyTimestampRules) that apply to them
+struct RuleArgs {
   const float* logits; int64_t logits_ld;   // row r at logits + r*logits_ld, V entries
   int R, V;
-  int64_t* tokens; int64_t token_stride;          // [R][stride], current length *d_ntok
+  int64_t token_stride;       // of the user's token buffer(s): [R][stride], current length *d_ntok
   const int* d_ntok;          // device: number of tokens currently in the longest row (== cached positions)
-  const int* lag;             // row r holds lag[r] fewer tokens, its sample_begin is lag[r] earlier; may be null
+  const int* lag;             // ragged prompts: row r holds lag[r] fewer tokens, its sample_begin is lag[r] earlier; may be null
   int sample_begin, eot, timestamp_begin, no_timestamps, max_initial_ts, suppress_blank, blank_token;
   const uint8_t* suppress_mask;
-  float* sum_logprobs;        // [R]
+  float* sum_logprobs;        // [R] in/out
+};
+
+// ---- sampling.hip --------------------------------------------------------------------------
+struct SampleArgs {
+  RuleArgs rules;
+  int64_t* tokens;            // [R][rules.token_stride]
   int64_t* step_tokens;       // [R] next-step input tokens (may be null)
   int* d_alive_step;          // device: set to ntok by every row whose sampled token is not EOT
   float* partials;            // scratch: greedy_sample_scratch_bytes(R, V)
@@ -309,9 +316,9 @@ struct SampleArgs {
   // optional: the final kernel also writes the next step's decoder input x_next[r][:] = tok_emb[token] + pos_emb[index of
   // the token] (model.py:236-240), so the step that follows needs no embedding launch; skipped when x_next is null
   float* x_next; const void* tok_emb; const float* pos_emb; int D, emb_f16, n_pos;
-  // optional: per-row timestamp-rule state kept by the final kernel, {last sampled token is a timestamp, the one before
-  // it is, value of the last sampled timestamp + 1 (0 = none), unused}, zeroed before the first sample of a sequence.
-  // With it the partial kernel does not walk the row's sampled tokens (three dependent round trips per step).
+  // per-row state kept by the final kernel, {last sampled token is a timestamp, the one before it is, value of the last
+  // sampled timestamp + 1 (0 = none), the row's trie node (PhraseArgs)}, zeroed before the first sample of a sequence: the
+  // partial kernel's timestamp window.  Required with timestamp rules (timestamp_begin >= 0) or a phrase list, else may be null.
   int* row_state;
 };
 // Phrase biasing inside the sampler (include/whisper_hip.h, wh_task_set_phrases): a token trie in CSR form, node 0 the root.
@@ -357,15 +364,9 @@ hipError_t launch_gather_tokens(const int64_t* src, int64_t stride, int R, int64
 // ---- beam.hip -------------------------------------------------------------------------------
 constexpr int BEAM_KMAX = 9;   // candidates per row = beam + 1, beam <= 8
 struct BeamArgs {
-  const float* logits; int64_t logits_ld;   // row r at logits + r*logits_ld, V entries
-  int R, V, G, K;                           // rows = segments x G beams; K = G + 1
-  const int64_t* tokens_in; int64_t* tokens_out; int64_t token_stride;   // [R][stride] each; rows hold *d_ntok tokens
-  const int* d_ntok;
-  const int* lag;                           // row r holds lag[r] fewer tokens and its sample_begin is lag[r] earlier (ragged
-                                            // prompts; equal within a beam group); may be null
-  int sample_begin, eot, timestamp_begin, no_timestamps, max_initial_ts, suppress_blank, blank_token;
-  const uint8_t* suppress_mask;
-  float* sum_logprobs;                      // [R] in/out
+  RuleArgs rules;                           // R rows = segments x G beams; token_stride of tokens_in / tokens_out
+  int G, K;                                 // K = G + 1
+  const int64_t* tokens_in; int64_t* tokens_out;   // [R][stride] each; rows hold *d_ntok tokens
   float* part_stat; float* part_val; int* part_idx;   // scratch (beam_scratch_carve)
   float* cand_lp; int* cand_tok;            // [R][BEAM_KMAX] top-K log-probabilities / tokens of every row
   int64_t* fin_tok; int* fin_len; float* fin_score; int* fin_count;   // [B][max_candidates][stride], [B][mc], [B][mc], [B]

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "kernels.h"
+#include "logit_rules.h"
 #include "sample_noise.h"
 
 using namespace whk;
@@ -143,38 +144,23 @@ int wht_score(int dtype, const void* xn, int64_t ldx, const void* W, int64_t ldw
                       dtype, (hipStream_t)stream);
 }
 
-// the two sampler launches of one decoding step (sampling.hip).  row_state: int [R][4], slot 3 = the row's trie node — a
-// test puts a row into any node there; `span` ([R][2] ints, scratch) is filled here from those nodes, as the previous
-// step's final kernel would have left it.  child_begin == NULL: the unbiased instantiations.
-int wht_greedy_sample(const float* logits, int64_t logits_ld, int R, int V, int64_t* tokens, int64_t token_stride,
-                      const int* d_ntok, const int* lag, int sample_begin, int eot, int timestamp_begin, int no_timestamps,
-                      int max_initial_ts, int suppress_blank, int blank_token, const uint8_t* suppress_mask,
-                      float* sum_logprobs, int64_t* step_tokens, int* d_alive_step, float* partials, size_t partials_bytes,
-                      float temperature, uint64_t seed, int* row_state, int n_nodes, int n_edges, const int* child_begin,
-                      const int* child_token, const int* child_node, const int* root_child, int* span, float boost,
-                      void* stream) {
-  if (R < 1 || V < 1 || partials_bytes < greedy_sample_scratch_bytes(R, V)) return hipErrorInvalidValue;
-  SampleArgs a;
-  memset(&a, 0, sizeof a);
-  a.logits = logits; a.logits_ld = logits_ld; a.R = R; a.V = V; a.tokens = tokens; a.token_stride = token_stride;
-  a.d_ntok = d_ntok; a.lag = lag; a.sample_begin = sample_begin; a.eot = eot; a.timestamp_begin = timestamp_begin;
-  a.no_timestamps = no_timestamps; a.max_initial_ts = max_initial_ts; a.suppress_blank = suppress_blank;
-  a.blank_token = blank_token; a.suppress_mask = suppress_mask; a.sum_logprobs = sum_logprobs; a.step_tokens = step_tokens;
-  a.d_alive_step = d_alive_step; a.partials = partials; a.row_state = row_state;
-  if (temperature > 0.f) {
-    a.inv_temperature = 1.0f / temperature;
-    a.seed_lo = (uint32_t)(seed & 0xffffffffu); a.seed_hi = (uint32_t)(seed >> 32);
-  }
-  if (!child_begin) return launch_greedy_sample(a, (hipStream_t)stream);
-  PhraseArgs ph;
-  memset(&ph, 0, sizeof ph);
-  ph.child_begin = child_begin; ph.child_token = child_token; ph.child_node = child_node; ph.root_child = root_child;
-  ph.span = span; ph.n_nodes = n_nodes; ph.n_edges = n_edges; ph.boost = boost;
-  const hipError_t e = launch_phrase_span(row_state, child_begin, n_nodes, R, span, (hipStream_t)stream);
-  if (e != hipSuccess) return e;
-  return launch_greedy_sample(a, (hipStream_t)stream, &ph);
+// the rows and stock logit rules of a sampler or beam launch (RuleArgs) from the flat arguments
+static RuleArgs rule_args(const float* logits, int64_t logits_ld, int R, int V, int64_t token_stride, const int* d_ntok,
+                          const int* lag, int sample_begin, int eot, int timestamp_begin, int no_timestamps, int max_initial_ts,
+                          int suppress_blank, int blank_token, const uint8_t* suppress_mask, float* sum_logprobs) {
+  RuleArgs r;
+  memset(&r, 0, sizeof r);
+  r.logits = logits; r.logits_ld = logits_ld; r.R = R; r.V = V; r.token_stride = token_stride; r.d_ntok = d_ntok; r.lag = lag;
+  r.sample_begin = sample_begin; r.eot = eot; r.timestamp_begin = timestamp_begin; r.no_timestamps = no_timestamps;
+  r.max_initial_ts = max_initial_ts; r.suppress_blank = suppress_blank; r.blank_token = blank_token;
+  r.suppress_mask = suppress_mask; r.sum_logprobs = sum_logprobs;
+  return r;
 }
-// the same two launches with repetition control (RepArgs) and, where child_begin is given, a phrase list as well
+
+// the two sampler launches of one decoding step (sampling.hip) with repetition control (RepArgs; (0, 1.0) = none).
+// row_state: int [R][4], slot 3 = the row's trie node — a test puts a row into any node there; `span` ([R][2] ints,
+// scratch) is filled here from those nodes, as the previous step's final kernel would have left it.  child_begin == NULL:
+// the unbiased instantiations.
 int wht_greedy_sample_rep(const float* logits, int64_t logits_ld, int R, int V, int64_t* tokens, int64_t token_stride,
                           const int* d_ntok, const int* lag, int sample_begin, int eot, int timestamp_begin, int no_timestamps,
                           int max_initial_ts, int suppress_blank, int blank_token, const uint8_t* suppress_mask,
@@ -185,11 +171,9 @@ int wht_greedy_sample_rep(const float* logits, int64_t logits_ld, int R, int V, 
   if (R < 1 || V < 1 || partials_bytes < greedy_sample_scratch_bytes(R, V)) return hipErrorInvalidValue;
   SampleArgs a;
   memset(&a, 0, sizeof a);
-  a.logits = logits; a.logits_ld = logits_ld; a.R = R; a.V = V; a.tokens = tokens; a.token_stride = token_stride;
-  a.d_ntok = d_ntok; a.lag = lag; a.sample_begin = sample_begin; a.eot = eot; a.timestamp_begin = timestamp_begin;
-  a.no_timestamps = no_timestamps; a.max_initial_ts = max_initial_ts; a.suppress_blank = suppress_blank;
-  a.blank_token = blank_token; a.suppress_mask = suppress_mask; a.sum_logprobs = sum_logprobs; a.step_tokens = step_tokens;
-  a.d_alive_step = d_alive_step; a.partials = partials; a.row_state = row_state;
+  a.rules = rule_args(logits, logits_ld, R, V, token_stride, d_ntok, lag, sample_begin, eot, timestamp_begin, no_timestamps,
+                      max_initial_ts, suppress_blank, blank_token, suppress_mask, sum_logprobs);
+  a.tokens = tokens; a.step_tokens = step_tokens; a.d_alive_step = d_alive_step; a.partials = partials; a.row_state = row_state;
   if (temperature > 0.f) {
     a.inv_temperature = 1.0f / temperature;
     a.seed_lo = (uint32_t)(seed & 0xffffffffu); a.seed_hi = (uint32_t)(seed >> 32);
@@ -203,6 +187,36 @@ int wht_greedy_sample_rep(const float* logits, int64_t logits_ld, int R, int V, 
   const hipError_t e = launch_phrase_span(row_state, child_begin, n_nodes, R, span, (hipStream_t)stream);
   if (e != hipSuccess) return e;
   return launch_greedy_sample(a, (hipStream_t)stream, &ph, &rep);
+}
+// ... and without it: launch_greedy_sample maps (0, 1.0) to the plain instantiations
+int wht_greedy_sample(const float* logits, int64_t logits_ld, int R, int V, int64_t* tokens, int64_t token_stride,
+                      const int* d_ntok, const int* lag, int sample_begin, int eot, int timestamp_begin, int no_timestamps,
+                      int max_initial_ts, int suppress_blank, int blank_token, const uint8_t* suppress_mask,
+                      float* sum_logprobs, int64_t* step_tokens, int* d_alive_step, float* partials, size_t partials_bytes,
+                      float temperature, uint64_t seed, int* row_state, int n_nodes, int n_edges, const int* child_begin,
+                      const int* child_token, const int* child_node, const int* root_child, int* span, float boost,
+                      void* stream) {
+  return wht_greedy_sample_rep(logits, logits_ld, R, V, tokens, token_stride, d_ntok, lag, sample_begin, eot, timestamp_begin,
+                               no_timestamps, max_initial_ts, suppress_blank, blank_token, suppress_mask, sum_logprobs,
+                               step_tokens, d_alive_step, partials, partials_bytes, temperature, seed, row_state, n_nodes,
+                               n_edges, child_begin, child_token, child_node, root_child, span, boost, 0, 1.0f, stream);
+}
+// the stock logit rules on the host (logit_rules.h; nothing is launched): mask[v] = 1 where token v is -inf for a row that
+// holds `row`: ntok - lag tokens, the last ntok - sample_begin of them sampled (both the longest row's, as on the device).
+// The timestamp window, returned as {last_ts, pen_ts, lo, hi}, comes from `row_state` [3] where given, else from the tokens.
+void wht_rule_mask(const int64_t* row, int ntok, int lag, int V, int sample_begin, int eot, int timestamp_begin,
+                   int no_timestamps, int max_initial_ts, int suppress_blank, int blank_token, const uint8_t* suppress_mask,
+                   const int* row_state, uint8_t* mask, int* window) {
+  const RuleArgs r = rule_args(nullptr, 0, 1, V, 0, nullptr, nullptr, sample_begin, eot, timestamp_begin, no_timestamps,
+                               max_initial_ts, suppress_blank, blank_token, suppress_mask, nullptr);
+  const RowPos pos = row_pos_of(r, ntok, lag);
+  int last = -1;                                     // the index in H of its last timestamp
+  for (int t = 0; t < pos.L && timestamp_begin >= 0; ++t)
+    if (row[pos.sample_begin + t] >= timestamp_begin) last = t;
+  const TsWindow w = row_state ? ts_window_of_state(r, pos, row_state[0], row_state[1], row_state[2])
+                               : ts_window_of_history(r, pos, row, last);
+  window[0] = w.last_ts; window[1] = w.pen_ts; window[2] = w.lo; window[3] = w.hi;
+  for (int v = 0; v < V; ++v) mask[v] = rule_masked(r, pos, w, v) ? 1 : 0;
 }
 size_t wht_greedy_sample_scratch_bytes(int R, int V) { return greedy_sample_scratch_bytes(R, V); }
 // the sampler's noise (sample_noise.h) on the host; nothing is launched.  wht_sample_uniform_range: the uniforms of `count`
@@ -281,11 +295,9 @@ int wht_beam_step(const float* logits, int64_t logits_ld, int B, int G, int K, i
   if (R < 1 || V < 1 || !scratch || scratch_bytes < beam_scratch_bytes(R, V)) return hipErrorInvalidValue;
   BeamArgs a;
   memset(&a, 0, sizeof a);
-  a.logits = logits; a.logits_ld = logits_ld; a.R = R; a.V = V; a.G = G; a.K = K;
-  a.tokens_in = tokens_in; a.tokens_out = tokens_out; a.token_stride = token_stride; a.d_ntok = d_ntok; a.lag = lag;
-  a.sample_begin = sample_begin; a.eot = eot; a.timestamp_begin = timestamp_begin; a.no_timestamps = no_timestamps;
-  a.max_initial_ts = max_initial_ts; a.suppress_blank = suppress_blank; a.blank_token = blank_token;
-  a.suppress_mask = suppress_mask; a.sum_logprobs = sum_logprobs;
+  a.rules = rule_args(logits, logits_ld, R, V, token_stride, d_ntok, lag, sample_begin, eot, timestamp_begin, no_timestamps,
+                      max_initial_ts, suppress_blank, blank_token, suppress_mask, sum_logprobs);
+  a.G = G; a.K = K; a.tokens_in = tokens_in; a.tokens_out = tokens_out;
   beam_scratch_carve(a, scratch, R, V);
   a.fin_tok = fin_tok; a.fin_len = fin_len; a.fin_score = fin_score; a.fin_count = fin_count;
   a.max_candidates = max_candidates; a.src = src; a.lcp = lcp; a.copy_from = copy_from; a.step_tokens = step_tokens;

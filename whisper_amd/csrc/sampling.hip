@@ -1,57 +1,29 @@
 // sampling.hip — the logits epilogue of DecodingTask._main_loop (whisper/decoding.py:696-703) for
 // greedy decoding, as two small kernels per step (vocabulary-parallel partials, per-row decision) with
 // no host synchronisation:
-//   SuppressBlank (decoding.py:423-430) -> SuppressTokens (:433-438) -> ApplyTimestampRules (:441-505)
-//   -> GreedyDecoder.update at temperature 0 (:277-293): argmax, log_softmax of the *filtered* logits,
+//   the stock logit rules and the timestamp mass rule (logit_rules.h)
+//   -> GreedyDecoder.update at temperature 0 (decoding.py:277-293): argmax, log_softmax of the *filtered* logits,
 //   sum_logprobs accumulation for rows not yet at EOT, EOT stickiness.
-// A single pass over the fp32 logits keeps separate online (max, sum-exp, arg-max) statistics for the text range [0, timestamp_begin) and the timestamp range, from which the
-// "timestamp probability mass > best text token" rule (:498-505) and the final normaliser follow
-// without re-reading the row.  The row's token history (needed by the pairing / monotonicity rules)
-// is scanned in parallel.
+// What the rules need of a row's token history sits in `row_state`, kept up to date by the final kernel.
 #include <string.h>
 
 #include "common.h"
 #include "kernels.h"
+#include "logit_rules.h"
 #include "sample_noise.h"
 
 namespace {
 
-struct Stat {           // online softmax statistics + first-index argmax of a range
-  float m, s; int idx;
-};
-__device__ __forceinline__ void stat_add(Stat& a, float x, int i) {
-  if (x == WH_NEG_INF) return;
-  if (x > a.m) { a.s = a.s * expf(a.m - x) + 1.0f; a.m = x; a.idx = i; }
-  else { a.s += expf(x - a.m); }   // x == a.m keeps the earlier (smaller) index: thread scan is ascending
-}
-__device__ __forceinline__ void stat_merge(Stat& a, float m, float s, int idx) {
-  if (m == WH_NEG_INF) return;
-  if (a.m == WH_NEG_INF) { a.m = m; a.s = s; a.idx = idx; return; }
-  if (m > a.m || (m == a.m && idx < a.idx)) {
-    a.s = a.s * expf(a.m - m) + s;
-    a.m = m; a.idx = idx;
-  } else {
-    a.s += s * expf(m - a.m);
-  }
-}
-__device__ __forceinline__ void stat_wave_reduce(Stat& a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m = __shfl_xor(a.m, o, 64);
-    const float s = __shfl_xor(a.s, o, 64);
-    const int idx = __shfl_xor(a.idx, o, 64);
-    stat_merge(a, m, s, idx);
-  }
-}
+using namespace whk;
 
-constexpr int SCHUNK = 1024;    // vocabulary entries per stage-1 workgroup (256 threads x 4)
+constexpr int SCHUNK = 1024;   // vocabulary entries per stage-1 workgroup (256 threads x 4)
 
 // Temperature sampling (GreedyDecoder.update at temperature > 0, decoding.py:281-283: Categorical(logits / T).sample())
 // as a Gumbel-max draw: argmax over the filtered entries of x / T + g, g = -log(-log(u)), u from a counter-based hash of
 // (seed, step, row, token) — one uniform per entry, no state, the same partial / final kernel structure as the arg-max.
 // The log-probability that is accumulated is the one of the UNSCALED filtered logits (decoding.py:285-287).
-struct Pick {           // best perturbed key of a range: key, the entry's logit, its index
-  float key, x; int idx;
+struct Pick {           // best perturbed key of a range: key, the entry's logit, its index; default: the empty range
+  float key = WH_NEG_INF, x = WH_NEG_INF; int idx = 0x7fffffff;
 };
 __device__ __forceinline__ void pick_merge(Pick& a, float key, float x, int idx) {
   if (idx == 0x7fffffff) return;
@@ -66,6 +38,23 @@ __device__ __forceinline__ void pick_wave_reduce(Pick& a) {
     pick_merge(a, key, x, idx);
   }
 }
+// the two ranges of a 256-thread workgroup in LDS, beside BlockStats (logit_rules.h): `publish` in front of its barrier
+struct BlockPicks {
+  float key[2][4], x[2][4]; int idx[2][4];
+  __device__ __forceinline__ void publish(Pick (&pk)[2]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      pick_wave_reduce(pk[g]);
+      if (lane == 0) { key[g][wave] = pk[g].key; x[g][wave] = pk[g].x; idx[g][wave] = pk[g].idx; }
+    }
+  }
+  __device__ __forceinline__ Pick range(int g) const {
+    Pick p;
+    for (int w = 0; w < 4; ++w) pick_merge(p, key[g][w], x[g][w], idx[g][w]);
+    return p;
+  }
+};
 // standard Gumbel noise for (seed, step, row, token): hash and uniform of sample_noise.h.  The 23-bit uniform lies in
 // [2^-24, 1 - 2^-24], strictly inside (0, 1) in fp32, so the noise is finite: about [-2.81, 16.64]
 __device__ __forceinline__ float gumbel(uint32_t seed_lo, uint32_t seed_hi, int step, int row, int v) {
@@ -101,62 +90,33 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
   __shared__ int sh_hist[REP ? HLEAD + HTILE : 1];
   __shared__ int sh_suffix[REP ? HLEAD : 1];
   __shared__ unsigned sh_pen[REP ? SCHUNK / 32 : 1], sh_ban[REP ? SCHUNK / 32 : 1];
-  __shared__ int sh_last_ts;
-  __shared__ float sh_m[2][4], sh_s[2][4];
-  __shared__ int sh_i[2][4];
-  __shared__ float sh_k[2][4], sh_x[2][4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ BlockStats<!SAMPLE> sh_st;       // when sampling, the index travels with the Pick
+  __shared__ BlockPicks sh_pk;
+  const RuleArgs& r = a.rules;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int c = blockIdx.x, k = blockIdx.y;
-  const float* x = a.logits + (int64_t)k * a.logits_ld;
+  const float* x = r.logits + (int64_t)k * r.logits_ld;
   float xv[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int v = c * SCHUNK + j * 256 + tid;
-    xv[j] = v < a.V ? x[v] : WH_NEG_INF;
+    xv[j] = v < r.V ? x[v] : WH_NEG_INF;
   }
   int rootc[4] = {-1, -1, -1, -1}, vsb = 0, vse = 0;
   if constexpr (BIAS) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int v = c * SCHUNK + j * 256 + tid;
-      if (v < a.V) rootc[j] = ph.root_child[v];
+      if (v < r.V) rootc[j] = ph.root_child[v];
     }
     vsb = load_agent_int(ph.span + 2 * k); vse = load_agent_int(ph.span + 2 * k + 1);
   }
-  const int vl = load_agent_int(a.lag ? a.lag + k : a.d_ntok), vn = load_agent_int(a.d_ntok);
-  const int lag = a.lag ? uniform(vl) : 0;   // ragged prompts: this row's indices sit lag earlier than the longest row's
-  const int ntok = uniform(vn) - lag;
-  const int sample_begin = a.sample_begin - lag;
-  const int64_t* row = a.tokens + (int64_t)k * a.token_stride;
-  const int L = ntok - sample_begin;
-  const int TB = a.timestamp_begin;       // < 0: timestamp rules disabled (without_timestamps)
-  const bool ts_rules = TB >= 0;
-
-  bool last_ts = false, pen_ts = false;
-  int ts_lo = 0, ts_hi = 0;              // forbidden timestamp interval [ts_lo, ts_hi)
-  if (ts_rules && a.row_state) {
-    // the final kernel of the previous step left what the rules need about this row's sampled tokens
-    const int s0 = load_agent_int(a.row_state + 4 * k), s1 = load_agent_int(a.row_state + 4 * k + 1),
-              s2 = load_agent_int(a.row_state + 4 * k + 2);
-    last_ts = (L >= 1) && uniform(s0) != 0;
-    pen_ts = (L < 2) || uniform(s1) != 0;
-    const int tv = uniform(s2);
-    if (tv > 0) { ts_lo = TB; ts_hi = (last_ts && !pen_ts) ? tv - 1 : tv; }
-  } else if (ts_rules) {
-    if (tid == 0) sh_last_ts = -1;
-    __syncthreads();
-    for (int t = tid; t < L; t += 256)
-      if (row[sample_begin + t] >= TB) atomicMax(&sh_last_ts, t);
-    __syncthreads();
-    last_ts = (L >= 1) && (row[ntok - 1] >= TB);
-    pen_ts = (L < 2) || (row[ntok - 2] >= TB);
-    if (sh_last_ts >= 0) {
-      const int t = (int)row[sample_begin + sh_last_ts];
-      ts_lo = TB;
-      ts_hi = (last_ts && !pen_ts) ? t : t + 1;
-    }
-  }
-  const int split = ts_rules ? TB : a.V;   // text range [0, split), timestamp range [split, V)
+  const RowPos pos = row_pos(r, k);
+  const int ntok = pos.ntok, sample_begin = pos.sample_begin, L = pos.L;
+  const int64_t* row = a.tokens + (int64_t)k * r.token_stride;
+  // the final kernel of the previous step left what the rules need about this row's sampled tokens
+  const TsWindow win = ts_window_load(r, pos, a.row_state, k);
+  const int split = r.timestamp_begin >= 0 ? r.timestamp_begin : r.V;   // text range [0, split), timestamp range [split, V)
 
   bool hit[4] = {false, false, false, false};
   if constexpr (BIAS) {
@@ -199,7 +159,7 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
       if (tid < HLEAD) sh_hist[tid] = lead;
       __syncthreads();
       const unsigned d = (unsigned)(tok - lo);
-      if (g < L && tok >= 0 && tok < a.eot && d < (unsigned)SCHUNK) {
+      if (g < L && tok >= 0 && tok < r.eot && d < (unsigned)SCHUNK) {
         if (pen_on) atomicOr(&sh_pen[d >> 5], 1u << (d & 31));
         if (ban_on && g >= nctx) {                         // H[g - nctx .. g - 1] == s ?  (i = g - nctx <= L - ngram)
           bool same = true;
@@ -211,31 +171,14 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
     __syncthreads();
   }
 
-  Stat st[2];
-  st[0] = Stat{WH_NEG_INF, 0.f, 0x7fffffff};
-  st[1] = Stat{WH_NEG_INF, 0.f, 0x7fffffff};
+  Stat<!SAMPLE> st[2];
   Pick pk[2];
-  pk[0] = Pick{WH_NEG_INF, WH_NEG_INF, 0x7fffffff};
-  pk[1] = pk[0];
-  const int step = ntok + lag;             // the common position counter: the same for every row of a step
+  const int step = ntok + pos.lag;         // the common position counter: the same for every row of a step
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int v = c * SCHUNK + j * 256 + tid;
-    if (v >= a.V) continue;
-    bool masked = a.suppress_mask && a.suppress_mask[v];
-    if (a.suppress_blank && L == 0 && (v == a.blank_token || v == a.eot)) masked = true;
-    if (ts_rules) {
-      if (v == a.no_timestamps) masked = true;
-      if (last_ts) {
-        if (pen_ts) { if (v >= TB) masked = true; }
-        else { if (v < a.eot) masked = true; }
-      }
-      if (v >= ts_lo && v < ts_hi) masked = true;
-      if (L == 0) {
-        if (v < TB) masked = true;
-        if (a.max_initial_ts >= 0 && v > TB + a.max_initial_ts) masked = true;
-      }
-    }
+    if (v >= r.V) continue;
+    bool masked = rule_masked(r, pos, win, v);
     if constexpr (REP) {
       if ((sh_ban[(j * 256 + tid) >> 5] >> (tid & 31)) & 1u) masked = true;      // NoRepeatNGram: -inf, like a suppressed token
     }
@@ -256,31 +199,15 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
       }
     }
   }
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    stat_wave_reduce(st[g]);
-    if constexpr (SAMPLE) pick_wave_reduce(pk[g]);
-    if (lane == 0) {
-      sh_m[g][wave] = st[g].m; sh_s[g][wave] = st[g].s; sh_i[g][wave] = SAMPLE ? pk[g].idx : st[g].idx;
-      if constexpr (SAMPLE) { sh_k[g][wave] = pk[g].key; sh_x[g][wave] = pk[g].x; }
-    }
-  }
-  __syncthreads();
+  if constexpr (SAMPLE) sh_pk.publish(pk);
+  sh_st.reduce(st);
   if (tid < 2) {
-    Stat t = Stat{WH_NEG_INF, 0.f, 0x7fffffff};
+    const auto t = sh_st.range(tid);
     float* o = a.partials + (((int64_t)k * nchunk + c) * 2 + tid) * PSTRIDE;   // nchunk == gridDim.x, passed as an argument:
                                                                                // gridDim sits in the implicit arguments (a second kernarg round trip)
-    if constexpr (SAMPLE) {
-      Pick p = Pick{WH_NEG_INF, WH_NEG_INF, 0x7fffffff};
-      for (int w = 0; w < 4; ++w) {
-        stat_merge(t, sh_m[tid][w], sh_s[tid][w], 0);
-        pick_merge(p, sh_k[tid][w], sh_x[tid][w], sh_i[tid][w]);
-      }
-      o[0] = t.m; o[1] = t.s; o[2] = __int_as_float(p.idx); o[3] = p.key; o[4] = p.x;
-    } else {
-      for (int w = 0; w < 4; ++w) stat_merge(t, sh_m[tid][w], sh_s[tid][w], sh_i[tid][w]);
-      o[0] = t.m; o[1] = t.s; o[2] = __int_as_float(t.idx);
-    }
+    o[0] = t.m; o[1] = t.s;
+    if constexpr (SAMPLE) { const Pick p = sh_pk.range(tid); o[2] = __int_as_float(p.idx); o[3] = p.key; o[4] = p.x; }
+    else o[2] = __int_as_float(t.idx);
   }
 }
 
@@ -295,95 +222,58 @@ __global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, in
   pin_kernargs(a);
   if constexpr (BIAS) pin_kernargs(ph);
   asm volatile("" ::"s"(nchunk));
-  __shared__ float sh_m[2][4], sh_s[2][4];
-  __shared__ int sh_i[2][4];
-  __shared__ float sh_k[2][4], sh_x[2][4];
-  __shared__ int sh_next;
-  __shared__ int sh_child;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int k = blockIdx.x;
+  __shared__ BlockStats<!SAMPLE> sh_st;
+  __shared__ BlockPicks sh_pk;
+  __shared__ int sh_next, sh_child;
+  const RuleArgs& r = a.rules;
+  const int tid = threadIdx.x, k = blockIdx.x;
   int vsb = 0, vse = 0;
   if constexpr (BIAS) { vsb = load_agent_int(ph.span + 2 * k); vse = load_agent_int(ph.span + 2 * k + 1); }
-  const int vl = load_agent_int(a.lag ? a.lag + k : a.d_ntok), vn = load_agent_int(a.d_ntok);
-  const int lag = a.lag ? uniform(vl) : 0;
-  const int ntok = uniform(vn) - lag;
-  int64_t* row = a.tokens + (int64_t)k * a.token_stride;
-  const bool ts_rules = a.timestamp_begin >= 0;
-  Stat st[2];
-  st[0] = Stat{WH_NEG_INF, 0.f, 0x7fffffff};
-  st[1] = Stat{WH_NEG_INF, 0.f, 0x7fffffff};
+  const RowPos pos = row_pos(r, k);
+  const int ntok = pos.ntok, lag = pos.lag;
+  int64_t* row = a.tokens + (int64_t)k * r.token_stride;
+  const bool ts_rules = r.timestamp_begin >= 0;
+  Stat<!SAMPLE> st[2];
   Pick pk[2];
-  pk[0] = Pick{WH_NEG_INF, WH_NEG_INF, 0x7fffffff};
-  pk[1] = pk[0];
   for (int c = tid; c < nchunk; c += 256) {
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       const float* o = a.partials + (((int64_t)k * nchunk + c) * 2 + g) * PSTRIDE;
       if constexpr (SAMPLE) {
-        stat_merge(st[g], o[0], o[1], 0);
+        stat_merge(st[g], Stat<false>{o[0], o[1]});
         pick_merge(pk[g], o[3], o[4], __float_as_int(o[2]));
       } else {
-        stat_merge(st[g], o[0], o[1], __float_as_int(o[2]));
+        stat_merge(st[g], Stat<true>{o[0], o[1], __float_as_int(o[2])});
       }
     }
   }
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    stat_wave_reduce(st[g]);
-    if constexpr (SAMPLE) pick_wave_reduce(pk[g]);
-    if (lane == 0) {
-      sh_m[g][wave] = st[g].m; sh_s[g][wave] = st[g].s; sh_i[g][wave] = SAMPLE ? pk[g].idx : st[g].idx;
-      if constexpr (SAMPLE) { sh_k[g][wave] = pk[g].key; sh_x[g][wave] = pk[g].x; }
-    }
-  }
+  if constexpr (SAMPLE) sh_pk.publish(pk);
   if constexpr (BIAS) { if (tid == 0) sh_child = -1; }
-  __syncthreads();
+  sh_st.reduce(st);
   if (tid == 0) {
     const int64_t last_tok = row[ntok - 1];
-    Stat tx = Stat{WH_NEG_INF, 0.f, 0x7fffffff}, ts = tx;
-    Pick ptx = Pick{WH_NEG_INF, WH_NEG_INF, 0x7fffffff}, pts = ptx;
-    for (int w = 0; w < 4; ++w) {
-      stat_merge(tx, sh_m[0][w], sh_s[0][w], SAMPLE ? 0 : sh_i[0][w]);
-      stat_merge(ts, sh_m[1][w], sh_s[1][w], SAMPLE ? 0 : sh_i[1][w]);
-      if constexpr (SAMPLE) {
-        pick_merge(ptx, sh_k[0][w], sh_x[0][w], sh_i[0][w]);
-        pick_merge(pts, sh_k[1][w], sh_x[1][w], sh_i[1][w]);
-      }
-    }
-    bool text_masked = false;
-    if (ts_rules) {
-      // decoding.py:498-505 — logsumexp of timestamp logprobs vs max text logprob (same normaliser)
-      Stat all = tx;
-      stat_merge(all, ts.m, ts.s, ts.idx);
-      if (all.m != WH_NEG_INF) {
-        const float lse_all = logf(all.s);
-        const float ts_lp_max = (ts.m - all.m) - lse_all;
-        const float ts_lse = (ts.m == WH_NEG_INF) ? WH_NEG_INF : ts_lp_max + logf(ts.s);
-        const float text_lp_max = (tx.m == WH_NEG_INF) ? WH_NEG_INF : (tx.m - all.m) - lse_all;
-        if (ts_lse > text_lp_max) text_masked = true;
-      }
-    }
-    Stat fin = ts;
-    if (!text_masked) { fin = tx; stat_merge(fin, ts.m, ts.s, ts.idx); }
-    int next = fin.idx;
-    // log_softmax(filtered)[next] = x - max - log(sum exp(x - max)); x[next] == max
-    float lp = -logf(fin.s);
+    bool text_masked;
+    const auto fin = allowed_range(sh_st.range(0), sh_st.range(1), ts_rules, &text_masked);
+    int next; float lp;
     if constexpr (SAMPLE) {                  // the Gumbel-max draw among the allowed entries; unscaled log-probability
-      Pick p = pts;
-      if (!text_masked) pick_merge(p, ptx.key, ptx.x, ptx.idx);
+      Pick p = sh_pk.range(1);
+      if (!text_masked) { const Pick ptx = sh_pk.range(0); pick_merge(p, ptx.key, ptx.x, ptx.idx); }
       next = p.idx;
       lp = (p.x - fin.m) - logf(fin.s);
+    } else {
+      next = fin.idx;
+      lp = -logf(fin.s);                     // log_softmax(filtered)[next] = x - max - log(sum exp(x - max)); x[next] == max
     }
     if (fin.m == WH_NEG_INF) { next = 0; lp = __builtin_nanf(""); }   // every logit filtered: argmax of all -inf
-    if (last_tok != a.eot) a.sum_logprobs[k] += lp;
-    else next = a.eot;
+    if (last_tok != r.eot) r.sum_logprobs[k] += lp;
+    else next = r.eot;
     row[ntok] = next;
     if (a.step_tokens) a.step_tokens[k] = next;
-    if (next != a.eot) *a.d_alive_step = ntok + lag;      // benign race: every writer stores the same value
+    if (next != r.eot) *a.d_alive_step = ntok + lag;      // benign race: every writer stores the same value
     sh_next = next;
-    if (a.row_state && ts_rules) {                         // what the next step's timestamp rules need about this row
+    if (ts_rules) {                                        // what the next step's window needs about this row (ts_window_of_state)
       int* st = a.row_state + 4 * k;
-      const bool is_ts = next >= a.timestamp_begin;
+      const bool is_ts = next >= r.timestamp_begin;
       st[1] = st[0];
       st[0] = is_ts ? 1 : 0;
       if (is_ts) st[2] = next + 1;
@@ -394,16 +284,16 @@ __global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, in
     __syncthreads();
     nxt = sh_next;
     sb = uniform(vsb); se = uniform(vse);
-    if (ntok == a.sample_begin - lag || sb < 0) sb = se = 0;     // a row's first sampled token leaves from the root
+    if (pos.L == 0 || sb < 0) sb = se = 0;     // a row's first sampled token leaves from the root
     if (se > ph.n_edges) se = ph.n_edges;
     if (sb + tid < se) { tk0 = ph.child_token[sb + tid]; cn0 = ph.child_node[sb + tid]; }
-    if (tid == 0 && nxt >= 0 && nxt < a.V) rootc = ph.root_child[nxt];
+    if (tid == 0 && nxt >= 0 && nxt < r.V) rootc = ph.root_child[nxt];
   }
   if (a.x_next) {                             // the next step's input row: embedding of the token just chosen, at its index
     if constexpr (!BIAS) __syncthreads();
     int tok = sh_next;
     if (tok < 0) tok = 0;
-    if (tok > a.V - 1) tok = a.V - 1;
+    if (tok > r.V - 1) tok = r.V - 1;
     if (ntok < a.n_pos) {
       const float* pp = a.pos_emb + (int64_t)ntok * a.D;
       float* xr = a.x_next + (int64_t)k * a.D;
@@ -512,14 +402,14 @@ size_t greedy_sample_scratch_bytes(int R, int V) { return (size_t)R * ((V + SCHU
 template <bool SAMPLE, bool BIAS>
 static void greedy_sample_launch(const SampleArgs& a, const PhraseArgs& ph, const RepArgs* rep, int nchunk, hipStream_t stream) {
   if (rep)      // repetition control lives in the partial kernel alone: the final kernel is the same with and without it
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS, true>), dim3(nchunk, a.R), dim3(256), 0, stream, a, nchunk, ph, *rep);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS, true>), dim3(nchunk, a.rules.R), dim3(256), 0, stream, a, nchunk, ph, *rep);
   else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS, false>), dim3(nchunk, a.R), dim3(256), 0, stream, a, nchunk, ph, RepArgs{0, 1.0f});
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_final_kernel<SAMPLE, BIAS>), dim3(a.R), dim3(256), 0, stream, a, nchunk, ph);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS, false>), dim3(nchunk, a.rules.R), dim3(256), 0, stream, a, nchunk, ph, RepArgs{0, 1.0f});
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_final_kernel<SAMPLE, BIAS>), dim3(a.rules.R), dim3(256), 0, stream, a, nchunk, ph);
 }
 
 hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const PhraseArgs* ph, const RepArgs* rep) {
-  const int nchunk = (a.V + SCHUNK - 1) / SCHUNK;
+  const int nchunk = (a.rules.V + SCHUNK - 1) / SCHUNK;
   if (!a.partials) return hipErrorInvalidValue;
   const bool sample = a.inv_temperature > 0.f;
   if (rep) {
@@ -527,6 +417,7 @@ hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const P
       return hipErrorInvalidValue;
     if (rep->ngram == 0 && rep->penalty == 1.0f) rep = nullptr;      // both off: the kernels of a plain decode
   }
+  if (a.rules.timestamp_begin >= 0 && !a.row_state) return hipErrorInvalidValue;   // the timestamp window comes from it
   if (ph) {
     if (!ph->child_begin || !ph->child_token || !ph->child_node || !ph->root_child || !ph->span || !a.row_state ||
         ph->n_nodes < 1 || ph->n_edges < 0)
