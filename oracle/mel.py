@@ -38,9 +38,10 @@ def mel_filterbank(n_mels: int, sr: int = 16000, n_fft: int = N_FFT) -> np.ndarr
     return weights.astype(np.float32)
 
 
-def log_mel_spectrogram(audio, filters, padding: int = 0, dtype=torch.float32) -> torch.Tensor:
+def log_mel_spectrogram(audio, filters, padding: int = 0, dtype=torch.float32, keep_dtype: bool = False) -> torch.Tensor:
     """audio.py:110-157 on CPU.  audio: (n,) or (B, n); filters: (n_mels, 201).  The max of audio.py:155
-    is global over the whole (batched) tensor, as in the reference."""
+    is global over the whole (batched) tensor, as in the reference.  keep_dtype: the result in `dtype`, without the
+    final rounding to float32 (the float64 restatements of the tests are compared with it to 1e-12)."""
     x = torch.as_tensor(np.asarray(audio) if not torch.is_tensor(audio) else audio).to(dtype)
     if padding > 0:
         x = torch.nn.functional.pad(x, (0, padding))                      # audio.py:145-146
@@ -55,4 +56,5 @@ def log_mel_spectrogram(audio, filters, padding: int = 0, dtype=torch.float32) -
     log_spec = torch.clamp(mel, min=1e-10).log10()                        # audio.py:154
     log_spec = torch.maximum(log_spec, log_spec.max() - 8.0)              # audio.py:155
     log_spec = (log_spec + 4.0) / 4.0                                     # audio.py:156
-    return (log_spec[0] if single else log_spec).float()
+    log_spec = log_spec[0] if single else log_spec
+    return log_spec if keep_dtype else log_spec.float()

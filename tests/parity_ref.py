@@ -9,6 +9,13 @@ import torch
 
 F32, F16, F64 = 0, 1, 2      # F64: references only (no rounding of intermediates)
 C_DOT = 2.0 ** -20
+# log-mel (tests/mel_ref.py): the fp32 spectrum X_k of a frame against float64 is within C_MEL * S_f, S_f = sum_j |x_j| w_j
+# the absolute sum of the windowed frame.  The numpy float32 model of mel_kernel (mel_ref.emulate_fp32: both folds, the
+# twiddle rotation re-read every 16 taps) was fitted at a peak of 2^-22.0 of S_f over twelve signal classes, all bins and
+# frames: a margin of 4, which tests/test_mel_ref_cpu.py asserts as "the model stays at or below a quarter of the output
+# bound" (it reaches 0.14).  Measured on |X| directly the restated model peaks at 2^-21.6, and at 2^-20.9 on the frames of
+# the `click` class whose S_f is one tap (test_spectrum_error_of_the_model)
+C_MEL = 2.0 ** -20
 # attention: C_ATT * (sum p |v| / sum p).  The VALU forms keep p in fp32; the MFMA forms (beam-group diag / mfma, flash)
 # round p to fp16 before the P.V product (2^-11 relative), and flash's unscaled form sums l from the fp32 p
 C_ATT_VALU = 2.0 ** -20

@@ -292,7 +292,7 @@ def _align_case(width, scale, nfr):
 
 
 @pytest.mark.parametrize("scale", [1.0, 0.5])
-@pytest.mark.parametrize("width", [1, 3, 7, 13, 15])
+@pytest.mark.parametrize("width", [1, 3, 5, 7, 9, 11, 13, 15])
 def test_align_batch(gpu_device, width, scale):
     """three ragged clips (tokens 2 / 9 / 40, frames 1 / 37 / 300) inside (40, 300) slabs of 320-key score rows; with
     row_begin = row_tail = 1 the two-token clip has no cost rows and nothing of its slab is written"""
@@ -516,7 +516,7 @@ EXPECTED_FORMS = sorted(
     [f"attn_generic<{t}>/{k}" for t in ("half", "float") for k in ("self", "cross")]
     + ["cross_qk<half>", "cross_qk<float>", "cross_qk_batch/mfma", "cross_qk_batch<float>"]
     + ["align/softmax_znorm", "align/head_mean", "align/end_to_end", "align/median_generic", "align/median_generic/passthrough"]
-    + [f"align/median<{w}>" for w in (1, 3, 7, 13)] + [f"align/median<{w}>/passthrough" for w in (3, 7, 13)]
+    + [f"align/median<{w}>" for w in (1, 3, 5, 7, 9, 11, 13)] + [f"align/median<{w}>/passthrough" for w in (3, 5, 7, 9, 11, 13)]
     + [f"mel_transpose<{i},{o}>" for i in ("half", "float") for o in ("half", "float")]
     + [f"stem/{c}<{t}>" for c in ("conv1", "conv2") for t in ("half", "float")]
     + ["gemm/vt_form", "embed<half>", "embed<float>", "no_speech", "gather_rows", "gather_tokens", "dtw", "dtw_batch"])

@@ -68,7 +68,7 @@ def test_cross_qk_bound(dtype):
 def test_alignment_bounds(scale):
     H, rb, rt = 3, 1, 1
     qk = pr.align_inputs(3, H, 40, 320, seed=int(scale * 10))
-    for width in (1, 3, 7, 13, 15):
+    for width in (1, 3, 5, 7, 9, 11, 13, 15):
         for (b, T, F) in ((0, 2, 3), (1, 9, 37), (2, 40, 300)):
             w0r, b0, w1r, b1, costr, bc = pr.align_chain_ref(qk[b].double(), T, F, scale, width, rb, rt)
             w0, w1, cost = pr.align_emulate(qk[b], T, F, scale, width, rb, rt)
@@ -122,7 +122,7 @@ def test_alignment_reference_is_the_oracles():
     assert ((w - mean) / std - pr.align_stage_a(qk, T, F, 0.5)[0]).abs().max().item() < 1e-11
     from oracle.timing import median_filter
     x = torch.randn(5, 37).float().numpy()
-    for width in (1, 3, 7, 13, 15):
+    for width in (1, 3, 5, 7, 9, 11, 13, 15):
         assert np.array_equal(median_filter(x, width), pr.median_f64(x, width))
 
 

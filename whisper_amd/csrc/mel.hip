@@ -55,7 +55,14 @@ __global__ __launch_bounds__(64) void mel_bands_kernel(const float* __restrict__
 // tap-major (`ev[tap][frame]`: the 8 frames of a tap are two broadcast ds_read_b128), and because those broadcast reads are
 // what the loop is bound by, ONE wave covers all 101 bin pairs of its eight frames (lane t: pairs t and t + 51) so every
 // read feeds 32 packed multiply-adds.  The twiddles advance by a rotation in registers, re-read exactly from the table
-// every RESYNC taps (fp32 drift over 16 rotations ~1e-6 relative, far inside the 1e-4 log-mel bar).
+// every RESYNC taps.
+// Accuracy is stated in the power domain, not as a flat bar on the logarithm (a quiet mel row beside a loud bin — a pure
+// tone, DC, a zero-padded window — is where the folds and the rotation cost digits, and there a flat 1e-4 is missed by a
+// CORRECT fp32 evaluation): the spectrum of a frame is within C_MEL * S_f of float64, S_f = sum_j |x_j| w_j and
+// C_MEL = 2^-20, and tests/mel_ref.py carries that through power, filter, log10 and the global floor as an interval
+// (tests/test_mel_parity_gpu.py holds the kernel to it per element).  A float32 model of this loop stays at or below 0.14
+// of the resulting bound with RESYNC = 16; rotated through all 208 taps without a re-read it reaches the bound itself
+// (0.4 - 1.06 over twelve signal classes), so the re-read is worth a factor of about eight.
 __global__ __launch_bounds__(MEL_THREADS) void mel_kernel(
     const float* __restrict__ audio, int64_t n_samples, int n_frames, int n_mels,
     const float* __restrict__ filters, const float* __restrict__ tables,  // cos[400] sin[400] win[400]
