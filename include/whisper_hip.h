@@ -349,6 +349,43 @@ int wh_task_set_phrases(wh_task *t, const wh_phrases *p, void *stream);
  * <= 0; WH_ERR_STATE while a begun loop is pending — all before any device work. */
 #define WH_REPETITION_MAX_NGRAM 16
 int wh_task_set_repetition(wh_task *t, int no_repeat_ngram_size, float repetition_penalty, void *stream);
+/* Per-token statistics of wh_task_greedy / wh_task_greedy_begin (arg-max and sampling): what every step knows about the
+ * distribution its token was chosen from.  That is the EDITED and FILTERED row — repetition penalty, phrase boost, n-gram
+ * ban, SuppressBlank / SuppressTokens / ApplyTimestampRules, and the text range dropped where the timestamp-mass rule
+ * fires — not the raw model distribution a teacher-forced wh_task_score reports.  All buffers are device memory, [n_rows]
+ * rows of `stride` columns, indexed like the token buffer: the values of the step that writes token column c of row r
+ * stand at [r][c] (row r's first sampled token at column sample_begin - lag[r]).  A step writes its one column and nothing
+ * else; columns never sampled keep what the caller put there.  Each pointer may be NULL on its own.
+ *   - token_logprobs [r][c], fp32: the very value the step adds to sum_logprobs[r], so that their sequential fp32 sum over
+ *     a row's columns reproduces sum_logprobs[r] bit for bit.
+ *   - entropy [r][c], fp32: -sum p log p in nats over the allowed entries of the row.
+ *   - top_tokens / top_logprobs [r][c][j], j < top_k (int32 / fp32): the top_k largest allowed entries, value descending,
+ *     the lower id first among equal values, their log-probabilities against the same normaliser as token_logprobs; where
+ *     the mass rule fires the list holds timestamps only; fewer than top_k finite entries are padded with (-1, -inf).  At
+ *     temperature 0 entry 0 is the chosen token and top_logprobs[r][c][0] == token_logprobs[r][c] bit for bit.  At
+ *     temperature > 0 the list ranks the UNSCALED edited logits, like the accumulated log-probability: the drawn token
+ *     need not be in it.
+ * A row that has reached <|endoftext|> stays there, accumulates nothing and writes 0, 0, (-1, -inf)...; a row with every
+ * logit filtered writes NaN (what it accumulates), NaN, (-1, -inf)....  The step logits the task holds are not modified.
+ * After a hand-off fallback's re-run from the prompt the columns simply hold the re-run's values.
+ * wh_task_step / wh_task_prefill / wh_task_score ignore the setting.  The beam loop keeps no per-step scores of a winner:
+ * wh_task_beam / wh_task_beam_begin return WH_ERR_STATE while statistics are set.  wh_task_greedy / wh_task_greedy_begin
+ * return WH_ERR_ARG when `stride` is smaller than their token_stride.
+ * Stream-ordered (the call does not wait); applies to the loops begun after the call; the buffers must stay valid until
+ * the setting is cleared — by s == NULL here or by wh_task_reset.  WH_ERR_ARG on a null task, top_k outside
+ * 0 .. WH_TOKEN_STATS_MAX_TOP, top_k > 0 with a null top pointer, every pointer null (or, with top_k == 0, both of
+ * token_logprobs and entropy: nothing would be written), stride < 1; WH_ERR_STATE while a begun loop is pending — all
+ * before any device work. */
+#define WH_TOKEN_STATS_MAX_TOP 8
+typedef struct wh_token_stats {
+  float *token_logprobs;             /* device [n_rows][stride], or NULL */
+  float *entropy;                    /* device [n_rows][stride], or NULL */
+  int32_t top_k;                     /* 0 .. WH_TOKEN_STATS_MAX_TOP */
+  int32_t *top_tokens;               /* device [n_rows][stride][top_k]; required when top_k > 0 */
+  float *top_logprobs;               /* device [n_rows][stride][top_k]; required when top_k > 0 */
+  int64_t stride;                    /* columns per row, >= the loop's token_stride */
+} wh_token_stats;
+int wh_task_set_token_stats(wh_task *t, const wh_token_stats *s, void *stream);
 /* number of cached self-attention positions of the longest row (the `offset` of model.py:234) */
 int wh_task_position(const wh_task *t);
 /* Introspection for tests and the benchmark.  what = 0: 1 when this task's decode step runs the cross attention with its

@@ -23,7 +23,7 @@ from . import audio as _audio
 from .align import align, align_batch
 from .audio import SAMPLE_RATE as _SAMPLE_RATE
 from .audio import log_mel_spectrogram, pad_or_trim
-from .decoding import (DecodingOptions, DecodingResult, ScoreResult, decode, decode_many, detect_language, run_in_lanes,
+from .decoding import (DecodingOptions, DecodingResult, DetailedDecodingResult, ScoreResult, decode, decode_many, detect_language, run_in_lanes,
                        run_interleaved, score)
 from .model import ModelDimensions, Whisper
 from .phrases import PhraseList

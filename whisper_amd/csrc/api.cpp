@@ -309,6 +309,8 @@ struct wh_task {
   int* phrase_root;        // [V] root child reached by every token, -1 = none
   int* phrase_span;        // [R][2] child_begin pair of every row's node ({0, 0} at the root)
   RepArgs rep; bool rep_on;       // repetition control (wh_task_set_repetition) of the loops begun from now on
+  wh_token_stats tstats; bool tstats_on;   // per-token statistics (wh_task_set_token_stats) of the loops begun from now on
+  void* samp_top;          // the sampler's per-chunk best entries, read only with statistics that ask for a top-k list
   void* beam_scratch;      // beam search partials / candidates (G > 1)
   int* beam_flags;         // [2][B] completion flags + [1] applied-update counter
   int* beam_lcp;           // [B][8][8] shared-history lengths of the rows of a segment + [R] first position to copy
@@ -342,6 +344,7 @@ struct wh_loop {
   SampleArgs sa; BeamArgs ba;
   PhraseArgs ph; bool biased;        // the greedy sampler's phrase arguments, when the task had a list at the loop's start
   RepArgs rep; bool rep_on;          // likewise its repetition control
+  TokenStatArgs ts; bool stats_on;   // likewise its per-token statistics
   bool fused_embed, pending, wait_due;
   int ntok, steps, ntok_at_copy, cur;
   int n_tokens;                      // result
@@ -443,6 +446,7 @@ static void task_carve(wh_task* t, void* base) {
   t->merge_cnt = (int*)c.take(R * H * 4);
   t->xh = c.take((R + 7) / 8 * 8 * D * 2);
   t->xcen = (float*)c.take(R * 4);
+  t->samp_top = c.take(greedy_sample_top_scratch_bytes((int)R, (int)V));      // last: everything above stays where it was
   t->total = align_up(c.off, 256);
 }
 
@@ -565,6 +569,7 @@ static int task_reset_impl(wh_task* t, void* stream_) {
   }
   t->phrases_on = false;                         // the sampler reads the derived tables only while a list is set
   t->rep_on = false; t->rep = RepArgs{0, 1.0f};
+  t->tstats_on = false;
   t->needs_reset = false;
   return WH_OK;
 }
@@ -624,6 +629,22 @@ extern "C" int wh_task_set_repetition(wh_task* t, int no_repeat_ngram_size, floa
   if (t->needs_reset) { const int rc = task_reset_impl(t, stream); if (rc != WH_OK) return rc; }
   t->rep = RepArgs{no_repeat_ngram_size, repetition_penalty};
   t->rep_on = no_repeat_ngram_size != 0 || repetition_penalty != 1.0f;
+  return WH_OK;
+}
+
+// Per-token statistics of the device-side greedy / sampling loop (sampling.hip, STATS).  Like repetition control the
+// setting lives on the host: the pointers travel as kernel arguments of the loops begun after the call.
+extern "C" int wh_task_set_token_stats(wh_task* t, const wh_token_stats* p, void* stream) {
+  TASK_ENTER(t);
+  if (!t) return WH_ERR_ARG;
+  if (!p) { t->tstats_on = false; return WH_OK; }
+  if (p->top_k < 0 || p->top_k > WH_TOKEN_STATS_MAX_TOP || p->stride < 1) return WH_ERR_ARG;
+  if (p->top_k > 0 && (!p->top_tokens || !p->top_logprobs)) return WH_ERR_ARG;
+  if (!p->token_logprobs && !p->entropy && !p->top_tokens && !p->top_logprobs) return WH_ERR_ARG;
+  if (p->top_k == 0 && !p->token_logprobs && !p->entropy) return WH_ERR_ARG;      // top buffers nothing would be written to
+  if (t->needs_reset) { const int rc = task_reset_impl(t, stream); if (rc != WH_OK) return rc; }
+  t->tstats = *p;
+  t->tstats_on = true;
   return WH_OK;
 }
 
@@ -1329,6 +1350,14 @@ static int greedy_start(wh_task* t) {
     HIPCHK(hipMemsetAsync(t->phrase_span, 0, (size_t)R * 8, s));
   }
   L->rep_on = t->rep_on; L->rep = t->rep;      // stateless: a hand-off fallback's re-run needs nothing put back
+  L->stats_on = t->tstats_on;                  // likewise: the re-run writes the same columns again
+  memset(&L->ts, 0, sizeof(L->ts));
+  if (L->stats_on) {
+    const wh_token_stats& q = t->tstats;
+    L->ts.token_logprob = q.token_logprobs; L->ts.entropy = q.entropy; L->ts.top_k = q.top_k;
+    L->ts.top_token = q.top_k > 0 ? q.top_tokens : nullptr; L->ts.top_logprob = q.top_k > 0 ? q.top_logprobs : nullptr;
+    L->ts.stride = q.stride; L->ts.scratch = t->samp_top;
+  }
   // the sampler also writes the next step's input row (token embedding + position): the step graph starts at layer 0
   L->fused_embed = !WH_DEV_FLAG("WH_NO_FUSED_EMBED");   // developer A/B switch
   if (L->fused_embed) {
@@ -1340,7 +1369,7 @@ static int greedy_start(wh_task* t) {
     sa.seed_lo = (uint32_t)(p->seed & 0xffffffffu); sa.seed_hi = (uint32_t)(p->seed >> 32);
   }
   sa.rules.logits = t->logits + (size_t)(n_sel - 1) * V; sa.rules.logits_ld = (int64_t)n_sel * V;
-  HIPCHK(launch_greedy_sample(sa, s, L->biased ? &ph : nullptr, L->rep_on ? &L->rep : nullptr));
+  HIPCHK(launch_greedy_sample(sa, s, L->biased ? &ph : nullptr, L->rep_on ? &L->rep : nullptr, L->stats_on ? &L->ts : nullptr));
   sa.rules.logits = t->logits; sa.rules.logits_ld = V;
   L->ntok = T0 + 1; L->steps = 1;
   L->pending = L->wait_due = false; L->ntok_at_copy = 0;
@@ -1442,7 +1471,7 @@ static int loop_pump(wh_task* t, bool block) {
         if (!(L->steps < p->max_steps && L->ntok <= p->n_ctx && L->ntok <= d.n_text_ctx)) break;
         int rc = step_run(t, s, t->loop_kind == LOOP_GREEDY && L->fused_embed);
         if (rc != WH_OK) return rc;
-        if (t->loop_kind == LOOP_GREEDY) HIPCHK(launch_greedy_sample(L->sa, s, L->biased ? &L->ph : nullptr, L->rep_on ? &L->rep : nullptr));
+        if (t->loop_kind == LOOP_GREEDY) HIPCHK(launch_greedy_sample(L->sa, s, L->biased ? &L->ph : nullptr, L->rep_on ? &L->rep : nullptr, L->stats_on ? &L->ts : nullptr));
         else { rc = beam_update(t, t->logits, d.n_vocab, 0); if (rc != WH_OK) return rc; }
         ++L->ntok; ++L->steps;
         if (L->pending && (L->steps & 7) == 2) L->wait_due = true;
@@ -1497,6 +1526,7 @@ static int greedy_check(const wh_task* t, const wh_greedy_params* p, const int64
   const int T0 = p->sample_begin;
   if (t->pos != 0 || T0 <= 0 || T0 > t->Tmax || p->max_steps <= 0) return WH_ERR_ARG;
   if (token_stride < (int64_t)T0 + p->max_steps) return WH_ERR_ARG;
+  if (t->tstats_on && t->tstats.stride < token_stride) return WH_ERR_ARG;      // the statistics are indexed by token column
   // ragged rows share one step counter: no row may reach the context limit before the step budget runs out
   if (t->lag_on && (T0 + p->max_steps > p->n_ctx || T0 + p->max_steps > d.n_text_ctx)) return WH_ERR_ARG;
   return WH_OK;
@@ -1508,6 +1538,7 @@ static int beam_check(const wh_task* t, const wh_beam_params* bp, const int64_t*
   if (!t || !bp || !tokens || !sum_logprobs || !fin_tokens || !fin_len || !fin_scores || !fin_count) return WH_ERR_ARG;
   if (t->phrases_on) return WH_ERR_STATE;      // the beam loop does not carry trie nodes through its row permutation
   if (t->rep_on) return WH_ERR_STATE;          // nor does beam.hip apply repetition control (the host loop's filters do)
+  if (t->tstats_on) return WH_ERR_STATE;       // nor does it keep a winner's per-step scores
   const wh_greedy_params* p = &bp->rules;
   const wh_dims& d = t->m->d;
   const int R = t->R, G = t->G, T0 = p->sample_begin;

@@ -29,28 +29,7 @@ using namespace whk;
 
 constexpr int BCHUNK = 1024;     // vocabulary entries per partial workgroup (256 threads x 4)
 constexpr int KMAX = whk::BEAM_KMAX;
-typedef Stat<false> BStat;       // the top K come from the selection below: no arg-max index in the statistics
-
-// larger value wins; equal values: smaller index wins
-__device__ __forceinline__ void best_merge(float& v, int& i, float v2, int i2) {
-  if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-}
-// arg-max over the 256 threads of a workgroup; every thread receives the winner.  sh_v/sh_i: [4] scratch.
-__device__ __forceinline__ void block_best(float& v, int& i, float* sh_v, int* sh_i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(v, o, 64);
-    const int i2 = __shfl_xor(i, o, 64);
-    best_merge(v, i, v2, i2);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();                        // scratch free (previous round read)
-  if (lane == 0) { sh_v[wave] = v; sh_i[wave] = i; }
-  __syncthreads();
-  v = sh_v[0]; i = sh_i[0];
-#pragma unroll
-  for (int w = 1; w < 4; ++w) best_merge(v, i, sh_v[w], sh_i[w]);
-}
+typedef Stat<false> BStat;       // the top K come from the selection (logit_rules.h: best_merge): no arg-max index in the statistics
 
 __global__ __launch_bounds__(256) void beam_partial_kernel(whk::BeamArgs a, int nchunk) {
   pin_kernargs(a);

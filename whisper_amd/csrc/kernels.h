@@ -346,11 +346,33 @@ struct RepArgs {
   int ngram;                  // 0: off
   float penalty;              // 1: off; finite and > 0
 };
+// Per-token statistics of the sampler (include/whisper_hip.h, wh_task_set_token_stats): what the step knows about the
+// distribution its token was chosen from — the edited and filtered row, the text range dropped where the timestamp mass rule
+// fires.  Every buffer is indexed by the COLUMN of the token buffer that receives the step's token (row r, column = the row's
+// own length, RowPos::ntok), so ragged prompts need nothing special; each may be null on its own.  A launch writes that one
+// column and nothing else.
+//   token_logprob [R][stride]         the fp32 value the final kernel adds to sum_logprobs
+//   entropy       [R][stride]         -sum p log p in nats over the allowed entries
+//   top_token / top_logprob [R][stride][top_k]   the top_k largest allowed entries, value descending, lower id first among
+//                 equal values; log-probabilities against the normaliser of token_logprob; padded with (-1, -inf).  They rank
+//                 the UNSCALED edited logits also at temperature > 0, like the accumulated log-probability.
+// A row already at eot writes 0, 0, (-1, -inf)...; a row with every logit filtered NaN, NaN, (-1, -inf)....
+constexpr int TOKEN_STATS_MAX_TOP = 8;
+struct TokenStatArgs {
+  float* token_logprob; float* entropy;
+  int* top_token; float* top_logprob;
+  int top_k;                  // 0 .. TOKEN_STATS_MAX_TOP; > 0 needs both top buffers and `scratch`
+  int64_t stride;             // columns per row of the buffers above, >= rules.token_stride
+  void* scratch;              // the chunks' best entries: greedy_sample_top_scratch_bytes(R, V); not read when top_k == 0
+};
 size_t greedy_sample_scratch_bytes(int R, int V);
+// what a launch with top_k > 0 needs on top of it, in TokenStatArgs::scratch (a plain decode's scratch stays what it is)
+size_t greedy_sample_top_scratch_bytes(int R, int V);
 // ph == nullptr: the unbiased instantiations, which never look at the phrase arguments; rep == nullptr (or {0, 1}): the
-// instantiations without repetition control, which never look at the row's history for it
+// instantiations without repetition control, which never look at the row's history for it; ts == nullptr: the instantiations
+// without statistics, which never look at the statistics arguments
 hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const PhraseArgs* ph = nullptr,
-                                const RepArgs* rep = nullptr);
+                                const RepArgs* rep = nullptr, const TokenStatArgs* ts = nullptr);
 // root[v] = child of the root reached by token v, else -1 (tokens outside [0, V) are ignored)
 hipError_t launch_phrase_root_table(const int* child_begin, const int* child_token, const int* child_node, int n_edges,
                                     int V, int* root, hipStream_t stream);

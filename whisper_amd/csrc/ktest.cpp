@@ -161,13 +161,14 @@ static RuleArgs rule_args(const float* logits, int64_t logits_ld, int R, int V, 
 // row_state: int [R][4], slot 3 = the row's trie node — a test puts a row into any node there; `span` ([R][2] ints,
 // scratch) is filled here from those nodes, as the previous step's final kernel would have left it.  child_begin == NULL:
 // the unbiased instantiations.
-int wht_greedy_sample_rep(const float* logits, int64_t logits_ld, int R, int V, int64_t* tokens, int64_t token_stride,
-                          const int* d_ntok, const int* lag, int sample_begin, int eot, int timestamp_begin, int no_timestamps,
-                          int max_initial_ts, int suppress_blank, int blank_token, const uint8_t* suppress_mask,
-                          float* sum_logprobs, int64_t* step_tokens, int* d_alive_step, float* partials, size_t partials_bytes,
-                          float temperature, uint64_t seed, int* row_state, int n_nodes, int n_edges, const int* child_begin,
-                          const int* child_token, const int* child_node, const int* root_child, int* span, float boost,
-                          int no_repeat_ngram_size, float repetition_penalty, void* stream) {
+// `ts` (per-token statistics, TokenStatArgs) is handed on as given; NULL: the instantiations without them.
+static int greedy_sample_any(const float* logits, int64_t logits_ld, int R, int V, int64_t* tokens, int64_t token_stride,
+                             const int* d_ntok, const int* lag, int sample_begin, int eot, int timestamp_begin, int no_timestamps,
+                             int max_initial_ts, int suppress_blank, int blank_token, const uint8_t* suppress_mask,
+                             float* sum_logprobs, int64_t* step_tokens, int* d_alive_step, float* partials, size_t partials_bytes,
+                             float temperature, uint64_t seed, int* row_state, int n_nodes, int n_edges, const int* child_begin,
+                             const int* child_token, const int* child_node, const int* root_child, int* span, float boost,
+                             int no_repeat_ngram_size, float repetition_penalty, const TokenStatArgs* ts, void* stream) {
   if (R < 1 || V < 1 || partials_bytes < greedy_sample_scratch_bytes(R, V)) return hipErrorInvalidValue;
   SampleArgs a;
   memset(&a, 0, sizeof a);
@@ -179,14 +180,53 @@ int wht_greedy_sample_rep(const float* logits, int64_t logits_ld, int R, int V, 
     a.seed_lo = (uint32_t)(seed & 0xffffffffu); a.seed_hi = (uint32_t)(seed >> 32);
   }
   const RepArgs rep{no_repeat_ngram_size, repetition_penalty};
-  if (!child_begin) return launch_greedy_sample(a, (hipStream_t)stream, nullptr, &rep);
+  if (!child_begin) return launch_greedy_sample(a, (hipStream_t)stream, nullptr, &rep, ts);
   PhraseArgs ph;
   memset(&ph, 0, sizeof ph);
   ph.child_begin = child_begin; ph.child_token = child_token; ph.child_node = child_node; ph.root_child = root_child;
   ph.span = span; ph.n_nodes = n_nodes; ph.n_edges = n_edges; ph.boost = boost;
   const hipError_t e = launch_phrase_span(row_state, child_begin, n_nodes, R, span, (hipStream_t)stream);
   if (e != hipSuccess) return e;
-  return launch_greedy_sample(a, (hipStream_t)stream, &ph, &rep);
+  return launch_greedy_sample(a, (hipStream_t)stream, &ph, &rep, ts);
+}
+int wht_greedy_sample_rep(const float* logits, int64_t logits_ld, int R, int V, int64_t* tokens, int64_t token_stride,
+                          const int* d_ntok, const int* lag, int sample_begin, int eot, int timestamp_begin, int no_timestamps,
+                          int max_initial_ts, int suppress_blank, int blank_token, const uint8_t* suppress_mask,
+                          float* sum_logprobs, int64_t* step_tokens, int* d_alive_step, float* partials, size_t partials_bytes,
+                          float temperature, uint64_t seed, int* row_state, int n_nodes, int n_edges, const int* child_begin,
+                          const int* child_token, const int* child_node, const int* root_child, int* span, float boost,
+                          int no_repeat_ngram_size, float repetition_penalty, void* stream) {
+  return greedy_sample_any(logits, logits_ld, R, V, tokens, token_stride, d_ntok, lag, sample_begin, eot, timestamp_begin,
+                           no_timestamps, max_initial_ts, suppress_blank, blank_token, suppress_mask, sum_logprobs, step_tokens,
+                           d_alive_step, partials, partials_bytes, temperature, seed, row_state, n_nodes, n_edges, child_begin,
+                           child_token, child_node, root_child, span, boost, no_repeat_ngram_size, repetition_penalty, nullptr,
+                           stream);
+}
+// ... with per-token statistics (TokenStatArgs) written to the column each row's token goes to: token_logprob / entropy
+// [R][stat_stride], top_token / top_logprob [R][stat_stride][top_k]; any of them may be NULL.  top_scratch: the chunks' best
+// entries (wht_greedy_sample_top_scratch_bytes; refused when smaller and top_k > 0).  The launcher's own refusals (top_k
+// outside 0 .. 8, a missing top buffer, no buffer at all, stat_stride < token_stride) come back unchanged, nothing launched.
+size_t wht_greedy_sample_top_scratch_bytes(int R, int V) { return greedy_sample_top_scratch_bytes(R, V); }
+int wht_greedy_sample_stats(const float* logits, int64_t logits_ld, int R, int V, int64_t* tokens, int64_t token_stride,
+                            const int* d_ntok, const int* lag, int sample_begin, int eot, int timestamp_begin, int no_timestamps,
+                            int max_initial_ts, int suppress_blank, int blank_token, const uint8_t* suppress_mask,
+                            float* sum_logprobs, int64_t* step_tokens, int* d_alive_step, float* partials, size_t partials_bytes,
+                            float temperature, uint64_t seed, int* row_state, int n_nodes, int n_edges, const int* child_begin,
+                            const int* child_token, const int* child_node, const int* root_child, int* span, float boost,
+                            int no_repeat_ngram_size, float repetition_penalty, float* token_logprob, float* entropy, int top_k,
+                            int* top_token, float* top_logprob, int64_t stat_stride, void* top_scratch, size_t top_scratch_bytes,
+                            void* stream) {
+  if (R < 1 || V < 1) return hipErrorInvalidValue;
+  if (top_k > 0 && top_scratch && top_scratch_bytes < greedy_sample_top_scratch_bytes(R, V)) return hipErrorInvalidValue;
+  TokenStatArgs ts;
+  memset(&ts, 0, sizeof ts);
+  ts.token_logprob = token_logprob; ts.entropy = entropy; ts.top_k = top_k; ts.top_token = top_token; ts.top_logprob = top_logprob;
+  ts.stride = stat_stride; ts.scratch = top_scratch;
+  return greedy_sample_any(logits, logits_ld, R, V, tokens, token_stride, d_ntok, lag, sample_begin, eot, timestamp_begin,
+                           no_timestamps, max_initial_ts, suppress_blank, blank_token, suppress_mask, sum_logprobs, step_tokens,
+                           d_alive_step, partials, partials_bytes, temperature, seed, row_state, n_nodes, n_edges, child_begin,
+                           child_token, child_node, root_child, span, boost, no_repeat_ngram_size, repetition_penalty, &ts,
+                           stream);
 }
 // ... and without it: launch_greedy_sample maps (0, 1.0) to the plain instantiations
 int wht_greedy_sample(const float* logits, int64_t logits_ld, int R, int V, int64_t* tokens, int64_t token_stride,

@@ -162,6 +162,28 @@ template <bool IDX> struct BlockStats : BlockStatsIdx<IDX> {
   }
 };
 
+// ---- selecting the best entries of a row (beam.hip: the K candidates; sampling.hip: the top-k alternatives) --------------------
+// larger value wins; equal values: smaller index wins
+__device__ __forceinline__ void best_merge(float& v, int& i, float v2, int i2) {
+  if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
+}
+// arg-max over the 256 threads of a workgroup; every thread receives the winner.  sh_v/sh_i: [4] scratch.
+__device__ __forceinline__ void block_best(float& v, int& i, float* sh_v, int* sh_i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(v, o, 64);
+    const int i2 = __shfl_xor(i, o, 64);
+    best_merge(v, i, v2, i2);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();                        // scratch free (previous round read)
+  if (lane == 0) { sh_v[wave] = v; sh_i[wave] = i; }
+  __syncthreads();
+  v = sh_v[0]; i = sh_i[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) best_merge(v, i, sh_v[w], sh_i[w]);
+}
+
 // ---- the timestamp mass rule (decoding.py:498-505) ------------------------------------------------------------------------
 // tx / ts: the statistics of the filtered text / timestamp range.  Where the timestamps together are more probable than the
 // best text token (logsumexp of their log-probabilities vs the largest text one, same normaliser) the text range is dropped.

@@ -61,7 +61,53 @@ __device__ __forceinline__ float gumbel(uint32_t seed_lo, uint32_t seed_hi, int 
   const float u = sample_uniform_of_hash(sample_hash(seed_lo, seed_hi, step, row, v));
   return -logf(-logf(u));
 }
-constexpr int PSTRIDE = 8;      // floats per (row, chunk, range) partial: m, s, idx | key, x (sampling)
+constexpr int PSTRIDE = 8;      // floats per (row, chunk, range) partial: m, s, idx | key, x (sampling) | m, s, t (STATS)
+
+// Per-token statistics (kernels.h TokenStatArgs).  The entropy of a range follows from a third online statistic next to
+// {m, s}: t = sum (x - m) exp(x - m), so that H = -sum p log p = log s - t / s.  A shift of the maximum by d = m_old - m_new
+// (<= 0) maps s -> s exp(d) and t -> (t + d s) exp(d).  It is a statistic of its own, with its own {m, s}: Stat<> and with it
+// the chosen token, its log-probability and the beam kernels stay what they are.  t <= 0 and s >= 1 hold in fp32 as they do
+// exactly (every term added is <= 0 resp. the maximum's own 1 is never scaled), so the entropy is never negative.
+// The empty range is m = -inf and is never shifted: -inf - x times s = 0 would be NaN.
+struct EStat { float m = WH_NEG_INF, s = 0.f, t = 0.f; };
+__device__ __forceinline__ void estat_add(EStat& a, float x) {
+  if (x == WH_NEG_INF) return;
+  if (a.m == WH_NEG_INF) { a.m = x; a.s = 1.0f; a.t = 0.f; return; }
+  if (x > a.m) { const float d = a.m - x, e = expf(d); a.t = (a.t + d * a.s) * e; a.s = a.s * e + 1.0f; a.m = x; }
+  else { const float d = x - a.m, e = expf(d); a.s += e; a.t += d * e; }
+}
+__device__ __forceinline__ void estat_merge(EStat& a, const EStat& b) {
+  if (b.m == WH_NEG_INF) return;
+  if (a.m == WH_NEG_INF) { a = b; return; }
+  if (b.m > a.m) { const float d = a.m - b.m, e = expf(d); a.t = (a.t + d * a.s) * e + b.t; a.s = a.s * e + b.s; a.m = b.m; }
+  else { const float d = b.m - a.m, e = expf(d); a.t += (b.t + d * b.s) * e; a.s += b.s * e; }
+}
+struct BlockEStats {            // beside BlockStats, like BlockPicks: `publish` in front of its barrier
+  float m[2][4], s[2][4], t[2][4];
+  __device__ __forceinline__ void publish(EStat (&st)[2]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1)
+        estat_merge(st[g], EStat{__shfl_xor(st[g].m, o, 64), __shfl_xor(st[g].s, o, 64), __shfl_xor(st[g].t, o, 64)});
+      if (lane == 0) { m[g][wave] = st[g].m; s[g][wave] = st[g].s; t[g][wave] = st[g].t; }
+    }
+  }
+  __device__ __forceinline__ EStat range(int g) const {
+    EStat r;
+    for (int w = 0; w < 4; ++w) estat_merge(r, EStat{m[g][w], s[g][w], t[g][w]});
+    return r;
+  }
+};
+constexpr int TOPMAX = whk::TOKEN_STATS_MAX_TOP;
+constexpr int TOP_CHUNKS = 64;                       // chunks whose best entries the final kernel can pool
+constexpr int TOP_POOL = 2 * TOP_CHUNKS * TOPMAX;    // both ranges x chunks x top_k
+// the chunks' best entries in TokenStatArgs::scratch: values [R][nchunk][2][TOPMAX], then indices likewise
+__device__ __forceinline__ float* top_part_val(const whk::TokenStatArgs& ts) { return (float*)ts.scratch; }
+__device__ __forceinline__ int* top_part_idx(const whk::TokenStatArgs& ts, int R, int nchunk) {
+  return (int*)ts.scratch + (int64_t)R * nchunk * 2 * TOPMAX;
+}
 
 // Stage 1: grid (chunks, rows).  Applies the filters to one 1024-entry slice of the row and reduces it
 // to two partial statistics (text range, timestamp range): {max, sum exp(x - max), first arg-max}.
@@ -81,12 +127,21 @@ constexpr int PSTRIDE = 8;      // floats per (row, chunk, range) partial: m, s,
 constexpr int HTILE = 256;      // tokens of a row's history per pass (== the workgroup size)
 constexpr int HLEAD = 16;       // tokens kept in front of a tile: the longest context (REP_MAX_NGRAM - 1) rounded up
 static_assert(whk::REP_MAX_NGRAM - 1 <= HLEAD, "a context must fit in front of a tile");
-template <bool SAMPLE, bool BIAS, bool REP>
-__global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, int nchunk, whk::PhraseArgs ph, whk::RepArgs rp) {
+// STATS (per-token statistics, kernels.h TokenStatArgs): the slice's entropy statistic goes out beside {m, s} in the partial's
+// spare slots, and with top_k > 0 its top_k best EDITED entries per range are selected as beam.hip selects a beam's candidates
+// (rounds of a workgroup arg-max over the four entries a thread holds) into the scratch of the statistics.  The logits are
+// read once, as without it.
+template <bool SAMPLE, bool BIAS, bool REP, bool STATS>
+__global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, int nchunk, whk::PhraseArgs ph, whk::RepArgs rp,
+                                                             whk::TokenStatArgs ts) {
   pin_kernargs(a);
   if constexpr (BIAS) pin_kernargs(ph);
   if constexpr (REP) pin_kernargs(rp);
+  if constexpr (STATS) pin_kernargs(ts);
   asm volatile("" ::"s"(nchunk));
+  __shared__ BlockEStats sh_es;      // unused, and so not allocated, without STATS
+  __shared__ float sh_bv[STATS ? 4 : 1];
+  __shared__ int sh_bi[STATS ? 4 : 1];
   __shared__ int sh_hist[REP ? HLEAD + HTILE : 1];
   __shared__ int sh_suffix[REP ? HLEAD : 1];
   __shared__ unsigned sh_pen[REP ? SCHUNK / 32 : 1], sh_ban[REP ? SCHUNK / 32 : 1];
@@ -173,6 +228,9 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
 
   Stat<!SAMPLE> st[2];
   Pick pk[2];
+  EStat est[2];
+  float xe[4] = {0.f, 0.f, 0.f, 0.f};      // STATS: the edited logits, valid where `live` has the entry's bit
+  unsigned live = 0;
   const int step = ntok + pos.lag;         // the common position counter: the same for every row of a step
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -192,6 +250,11 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
     }
     if constexpr (BIAS) { if (hit[j]) xj += ph.boost; }
     if (v < split) stat_add(st[0], xj, v); else stat_add(st[1], xj, v);
+    if constexpr (STATS) {
+      if (v < split) estat_add(est[0], xj); else estat_add(est[1], xj);
+      xe[j] = xj;
+      live |= (xj != WH_NEG_INF ? 1u : 0u) << j;
+    }
     if constexpr (SAMPLE) {
       if (xj != WH_NEG_INF) {
         const float key = xj * a.inv_temperature + gumbel(a.seed_lo, a.seed_hi, step, k, v);
@@ -200,6 +263,7 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
     }
   }
   if constexpr (SAMPLE) sh_pk.publish(pk);
+  if constexpr (STATS) sh_es.publish(est);
   sh_st.reduce(st);
   if (tid < 2) {
     const auto t = sh_st.range(tid);
@@ -208,6 +272,38 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
     o[0] = t.m; o[1] = t.s;
     if constexpr (SAMPLE) { const Pick p = sh_pk.range(tid); o[2] = __int_as_float(p.idx); o[3] = p.key; o[4] = p.x; }
     else o[2] = __int_as_float(t.idx);
+    if constexpr (STATS) { const EStat e = sh_es.range(tid); o[5] = e.m; o[6] = e.s; o[7] = e.t; }
+  }
+  if constexpr (STATS) {
+    const int K = ts.top_k;                 // uniform; 0: log-probability and entropy alone
+    if (K > 0) {
+      const int lo = c * SCHUNK, hi = (lo + SCHUNK < r.V) ? lo + SCHUNK : r.V;
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        float* pv = top_part_val(ts) + (((int64_t)k * nchunk + c) * 2 + g) * TOPMAX;
+        int* pi = top_part_idx(ts, r.R, nchunk) + (((int64_t)k * nchunk + c) * 2 + g) * TOPMAX;
+        const bool has = g == 0 ? lo < split : hi > split;        // uniform
+        if (!has) {
+          if (tid < K) { pv[tid] = WH_NEG_INF; pi[tid] = NO_IDX; }
+          continue;
+        }
+        unsigned avail = 0;                 // live entries of this range not yet taken
+#pragma unroll
+        for (int j = 0; j < 4; ++j) avail |= ((((live >> j) & 1u) != 0 && (lo + j * 256 + tid < split) == (g == 0)) ? 1u : 0u) << j;
+        for (int kk = 0; kk < K; ++kk) {
+          float bv = WH_NEG_INF; int bi = NO_IDX;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const bool on = ((avail >> j) & 1u) != 0;
+            best_merge(bv, bi, on ? xe[j] : WH_NEG_INF, on ? lo + j * 256 + tid : NO_IDX);
+          }
+          block_best(bv, bi, sh_bv, sh_bi);
+          if (tid == 0) { pv[kk] = bv; pi[kk] = bi; }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) avail &= ~(((lo + j * 256 + tid == bi) ? 1u : 0u) << j);
+        }
+      }
+    }
   }
 }
 
@@ -217,11 +313,19 @@ __global__ __launch_bounds__(256) void greedy_partial_kernel(whk::SampleArgs a, 
 // root.  The whole workgroup finds it in one round trip that starts as soon as the token is known and runs beside the
 // embedding gather: thread i asks for child i of the node (token and target), thread 0 for root_child[token]; a loop only
 // for a node of more than 256 children.  Thread 0 stores the node (row_state slot 3) and its child_begin pair (`span`).
-template <bool SAMPLE, bool BIAS>
-__global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, int nchunk, whk::PhraseArgs ph) {
+// STATS: the row's entropy statistic is merged beside {m, s}; thread 0 writes the step's log-probability (the value it
+// accumulates) and entropy.  With top_k > 0 the chunks' best entries are pooled in LDS while the partials are merged, the text
+// range's are dropped where the mass rule fired, and top_k rounds of a workgroup arg-max pick the row's — beam_row_kernel's
+// selection, behind everything the next step waits for.
+template <bool SAMPLE, bool BIAS, bool STATS>
+__global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, int nchunk, whk::PhraseArgs ph, whk::TokenStatArgs ts) {
   pin_kernargs(a);
   if constexpr (BIAS) pin_kernargs(ph);
+  if constexpr (STATS) pin_kernargs(ts);
   asm volatile("" ::"s"(nchunk));
+  __shared__ BlockEStats sh_es;      // unused, and so not allocated, without STATS
+  __shared__ float sh_bv[STATS ? 4 : 1], pool_v[STATS ? TOP_POOL : 1], sh_norm[2];
+  __shared__ int sh_bi[STATS ? 4 : 1], pool_i[STATS ? TOP_POOL : 1], sh_kind;
   __shared__ BlockStats<!SAMPLE> sh_st;
   __shared__ BlockPicks sh_pk;
   __shared__ int sh_next, sh_child;
@@ -235,10 +339,12 @@ __global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, in
   const bool ts_rules = r.timestamp_begin >= 0;
   Stat<!SAMPLE> st[2];
   Pick pk[2];
+  EStat est[2];
   for (int c = tid; c < nchunk; c += 256) {
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       const float* o = a.partials + (((int64_t)k * nchunk + c) * 2 + g) * PSTRIDE;
+      if constexpr (STATS) estat_merge(est[g], EStat{o[5], o[6], o[7]});
       if constexpr (SAMPLE) {
         stat_merge(st[g], Stat<false>{o[0], o[1]});
         pick_merge(pk[g], o[3], o[4], __float_as_int(o[2]));
@@ -249,6 +355,15 @@ __global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, in
   }
   if constexpr (SAMPLE) sh_pk.publish(pk);
   if constexpr (BIAS) { if (tid == 0) sh_child = -1; }
+  const int K = STATS ? ts.top_k : 0, npool = 2 * nchunk * K;      // uniform
+  if constexpr (STATS) {
+    sh_es.publish(est);
+    for (int e = tid; e < npool; e += 256) {              // entry e: (chunk, range) = e / K, rank e % K
+      const int cg = e / K, kk = e - cg * K;
+      pool_v[e] = top_part_val(ts)[((int64_t)k * nchunk * 2 + cg) * TOPMAX + kk];
+      pool_i[e] = top_part_idx(ts, r.R, nchunk)[((int64_t)k * nchunk * 2 + cg) * TOPMAX + kk];
+    }
+  }
   sh_st.reduce(st);
   if (tid == 0) {
     const int64_t last_tok = row[ntok - 1];
@@ -267,6 +382,17 @@ __global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, in
     if (fin.m == WH_NEG_INF) { next = 0; lp = __builtin_nanf(""); }   // every logit filtered: argmax of all -inf
     if (last_tok != r.eot) r.sum_logprobs[k] += lp;
     else next = r.eot;
+    if constexpr (STATS) {
+      // kind 0: the list of the allowed entries, 1: of the timestamps alone (mass rule), 2: padding only
+      const bool at_eot = last_tok == r.eot, none = fin.m == WH_NEG_INF;
+      EStat ef = sh_es.range(1);
+      if (!text_masked) { ef = sh_es.range(0); estat_merge(ef, sh_es.range(1)); }
+      const int64_t col = (int64_t)k * ts.stride + ntok;
+      if (ts.token_logprob) ts.token_logprob[col] = at_eot ? 0.f : lp;
+      if (ts.entropy) ts.entropy[col] = at_eot ? 0.f : none ? __builtin_nanf("") : logf(ef.s) - ef.t / ef.s;
+      sh_kind = (at_eot || none) ? 2 : text_masked ? 1 : 0;
+      sh_norm[0] = fin.m; sh_norm[1] = none ? 0.f : logf(fin.s);
+    }
     row[ntok] = next;
     if (a.step_tokens) a.step_tokens[k] = next;
     if (next != r.eot) *a.d_alive_step = ntok + lag;      // benign race: every writer stores the same value
@@ -318,6 +444,37 @@ __global__ __launch_bounds__(256) void greedy_final_kernel(whk::SampleArgs a, in
       if (ns > 0) { b = ph.child_begin[ns]; e = ph.child_begin[ns + 1]; }
       a.row_state[4 * k + 3] = ns;
       ph.span[2 * k] = b; ph.span[2 * k + 1] = e;
+    }
+  }
+  if constexpr (STATS) {
+    if (K > 0) {
+      __syncthreads();
+      const int kind = uniform(sh_kind);      // the same in every lane: the branches below stay scalar
+      const float M = sh_norm[0], LS = sh_norm[1];
+      const int64_t col = ((int64_t)k * ts.stride + ntok) * K;
+      if (kind == 2) {
+        if (tid < K) { ts.top_token[col + tid] = -1; ts.top_logprob[col + tid] = WH_NEG_INF; }
+        return;
+      }
+      if (kind == 1) {                      // entry e belongs to range (e / K) & 1: drop the text range's
+        for (int e = tid; e < npool; e += 256)
+          if (((e / K) & 1) == 0) pool_v[e] = WH_NEG_INF;
+      }
+      for (int kk = 0; kk < K; ++kk) {      // a thread reads the pool entries it wrote itself: no barrier in between
+        float bv = WH_NEG_INF; int bi = NO_IDX;
+        for (int e = tid; e < npool; e += 256)
+          if (pool_v[e] != WH_NEG_INF) best_merge(bv, bi, pool_v[e], pool_i[e]);
+        block_best(bv, bi, sh_bv, sh_bi);
+        if (tid == 0) {
+          // at temperature 0 entry 0 is the chosen token: -log s as the accumulated value is formed, not 0 - log s (-0 vs +0)
+          float v = (!SAMPLE && kk == 0) ? -LS : (bv - M) - LS;
+          if (bv == WH_NEG_INF) v = WH_NEG_INF;
+          ts.top_token[col + kk] = (bi == NO_IDX) ? -1 : bi;
+          ts.top_logprob[col + kk] = v;
+        }
+        for (int e = tid; e < npool; e += 256)
+          if (pool_i[e] == bi) pool_v[e] = WH_NEG_INF;     // a token sits in exactly one (chunk, range)
+      }
     }
   }
 }
@@ -398,19 +555,36 @@ __global__ void gather_tokens_kernel(const int64_t* __restrict__ src, int64_t st
 namespace whk {
 
 size_t greedy_sample_scratch_bytes(int R, int V) { return (size_t)R * ((V + SCHUNK - 1) / SCHUNK) * 2 * PSTRIDE * sizeof(float); }
+size_t greedy_sample_top_scratch_bytes(int R, int V) { return (size_t)R * ((V + SCHUNK - 1) / SCHUNK) * 2 * TOPMAX * 2 * 4; }
 
-template <bool SAMPLE, bool BIAS>
-static void greedy_sample_launch(const SampleArgs& a, const PhraseArgs& ph, const RepArgs* rep, int nchunk, hipStream_t stream) {
+template <bool SAMPLE, bool BIAS, bool STATS>
+static void greedy_sample_launch3(const SampleArgs& a, const PhraseArgs& ph, const RepArgs* rep, const TokenStatArgs& ts, int nchunk,
+                                  hipStream_t stream) {
   if (rep)      // repetition control lives in the partial kernel alone: the final kernel is the same with and without it
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS, true>), dim3(nchunk, a.rules.R), dim3(256), 0, stream, a, nchunk, ph, *rep);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS, true, STATS>), dim3(nchunk, a.rules.R), dim3(256), 0, stream, a, nchunk, ph, *rep, ts);
   else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS, false>), dim3(nchunk, a.rules.R), dim3(256), 0, stream, a, nchunk, ph, RepArgs{0, 1.0f});
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_final_kernel<SAMPLE, BIAS>), dim3(a.rules.R), dim3(256), 0, stream, a, nchunk, ph);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_partial_kernel<SAMPLE, BIAS, false, STATS>), dim3(nchunk, a.rules.R), dim3(256), 0, stream, a, nchunk, ph, RepArgs{0, 1.0f}, ts);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(greedy_final_kernel<SAMPLE, BIAS, STATS>), dim3(a.rules.R), dim3(256), 0, stream, a, nchunk, ph, ts);
+}
+template <bool SAMPLE, bool BIAS>
+static void greedy_sample_launch(const SampleArgs& a, const PhraseArgs& ph, const RepArgs* rep, const TokenStatArgs* ts, int nchunk,
+                                 hipStream_t stream) {
+  if (ts) { greedy_sample_launch3<SAMPLE, BIAS, true>(a, ph, rep, *ts, nchunk, stream); return; }
+  TokenStatArgs none;
+  memset(&none, 0, sizeof(none));
+  greedy_sample_launch3<SAMPLE, BIAS, false>(a, ph, rep, none, nchunk, stream);
 }
 
-hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const PhraseArgs* ph, const RepArgs* rep) {
+hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const PhraseArgs* ph, const RepArgs* rep,
+                                const TokenStatArgs* ts) {
   const int nchunk = (a.rules.V + SCHUNK - 1) / SCHUNK;
   if (!a.partials) return hipErrorInvalidValue;
+  if (ts) {     // refused before anything is launched: nothing is written
+    if (ts->top_k < 0 || ts->top_k > TOKEN_STATS_MAX_TOP || ts->stride < 1 || ts->stride < a.rules.token_stride)
+      return hipErrorInvalidValue;
+    if (ts->top_k > 0 && (!ts->top_token || !ts->top_logprob || !ts->scratch || nchunk > TOP_CHUNKS)) return hipErrorInvalidValue;
+    if (!ts->token_logprob && !ts->entropy && !(ts->top_k > 0)) return hipErrorInvalidValue;
+  }
   const bool sample = a.inv_temperature > 0.f;
   if (rep) {
     if (rep->ngram < 0 || rep->ngram > REP_MAX_NGRAM || !(rep->penalty > 0.f) || !(rep->penalty <= 3.402823466e38f))
@@ -422,13 +596,13 @@ hipError_t launch_greedy_sample(const SampleArgs& a, hipStream_t stream, const P
     if (!ph->child_begin || !ph->child_token || !ph->child_node || !ph->root_child || !ph->span || !a.row_state ||
         ph->n_nodes < 1 || ph->n_edges < 0)
       return hipErrorInvalidValue;
-    if (sample) greedy_sample_launch<true, true>(a, *ph, rep, nchunk, stream);
-    else greedy_sample_launch<false, true>(a, *ph, rep, nchunk, stream);
+    if (sample) greedy_sample_launch<true, true>(a, *ph, rep, ts, nchunk, stream);
+    else greedy_sample_launch<false, true>(a, *ph, rep, ts, nchunk, stream);
   } else {
     PhraseArgs none;
     memset(&none, 0, sizeof(none));
-    if (sample) greedy_sample_launch<true, false>(a, none, rep, nchunk, stream);
-    else greedy_sample_launch<false, false>(a, none, rep, nchunk, stream);
+    if (sample) greedy_sample_launch<true, false>(a, none, rep, ts, nchunk, stream);
+    else greedy_sample_launch<false, false>(a, none, rep, ts, nchunk, stream);
   }
   return hipGetLastError();
 }

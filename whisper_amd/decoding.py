@@ -16,7 +16,7 @@ work happens:
 from __future__ import annotations
 
 import contextlib
-from dataclasses import dataclass, field, replace
+from dataclasses import dataclass, field, fields as dataclass_fields, replace
 from typing import TYPE_CHECKING, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -132,6 +132,60 @@ class DecodingResult:
     no_speech_prob: float = np.nan
     temperature: float = np.nan
     compression_ratio: float = np.nan
+
+
+@dataclass(frozen=True)
+class DetailedDecodingResult(DecodingResult):
+    """`DecodingResult` plus what every step knew about the distribution its token was chosen from: the edited and filtered
+    row (repetition control, phrase boost, the stock logit filters, the timestamp-mass rule), not the raw model's.  One entry
+    per token of `tokens`, then one for the closing <|endoftext|> where the row reached it (the convention of `ScoreResult`:
+    sum(token_logprobs) / (len(tokens) + 1) is avg_logprob).  `top_tokens[i]` / `top_logprobs[i]`: the `top_logprobs=k` most
+    probable allowed tokens at step i, best first, padded with (-1, -inf); empty lists with k = 0."""
+    token_logprobs: List[float] = field(default_factory=list)
+    token_entropies: List[float] = field(default_factory=list)
+    top_tokens: List[List[int]] = field(default_factory=list)
+    top_logprobs: List[List[float]] = field(default_factory=list)
+
+
+MAX_TOP_LOGPROBS = 8            # WH_TOKEN_STATS_MAX_TOP (include/whisper_hip.h)
+
+
+def check_token_stats(token_logprobs=False, top_logprobs=0) -> Tuple[bool, int]:
+    """the two per-token statistics options as (bool, int); ValueError for a `top_logprobs` outside 0 .. 8 or not an integer.
+    `top_logprobs > 0` implies `token_logprobs`."""
+    k = 0 if top_logprobs is None else top_logprobs
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"top_logprobs must be an integer from 0 (off) to {MAX_TOP_LOGPROBS} (got {top_logprobs!r})")
+    if not isinstance(token_logprobs, (bool, np.bool_)) and token_logprobs is not None:
+        raise ValueError(f"token_logprobs must be a bool (got {token_logprobs!r})")
+    return bool(token_logprobs) or k > 0, int(k)
+
+
+def step_token_stats(logits: Tensor, chosen: Tensor, ended: Tensor, top_k: int):
+    """The four per-token quantities of one step from the FILTERED logits (rows x vocabulary), in torch fp32, as the
+    device-side loop defines them: log-probability of `chosen`, entropy in nats over the finite entries, the `top_k` largest
+    entries (value descending, lower id first among equal values) with their log-probabilities, padded with (-1, -inf).
+    Rows with `ended` (already at <|endoftext|>) give 0, 0, padding; rows with every logit filtered NaN, NaN, padding."""
+    x = logits.float()
+    R, V = x.shape
+    logp = F.log_softmax(x, dim=-1)
+    finite = torch.isfinite(x)
+    ent = -(torch.where(finite, logp.exp() * logp, torch.zeros_like(logp))).sum(dim=-1)
+    lp = logp.gather(1, chosen.view(-1, 1).clamp(0, V - 1))[:, 0]
+    none = ~finite.any(dim=-1)
+    nan = torch.full_like(lp, float("nan"))
+    lp, ent = torch.where(none, nan, lp), torch.where(none, nan, ent)
+    lp, ent = lp.masked_fill(ended, 0.0), ent.masked_fill(ended, 0.0)
+    top_t = torch.full((R, top_k), -1, dtype=torch.int64, device=x.device)
+    top_v = torch.full((R, top_k), float("-inf"), dtype=torch.float32, device=x.device)
+    if top_k:
+        # a stable descending sort keeps the lower id first among equal values
+        order = torch.sort(x, dim=-1, descending=True, stable=True).indices[:, :top_k]
+        vals = logp.gather(1, order)
+        ok = finite.gather(1, order) & ~(ended | none).view(-1, 1)
+        top_t[:, : order.shape[1]] = torch.where(ok, order, torch.full_like(order, -1))
+        top_v[:, : order.shape[1]] = torch.where(ok, vals, torch.full_like(vals, float("-inf")))
+    return lp, ent, top_t, top_v
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -588,8 +642,14 @@ class DecodingTask:
 
     def __init__(self, model: "Whisper", options: DecodingOptions, prompts: Optional[Sequence[Sequence[int]]] = None,
                  phrases: Optional[Union[PhraseList, Sequence]] = None, no_repeat_ngram_size: int = 0,
-                 repetition_penalty: float = 1.0):
-        """`no_repeat_ngram_size` / `repetition_penalty` (no counterpart in the reference; keywords, because DecodingOptions
+                 repetition_penalty: float = 1.0, token_logprobs: bool = False, top_logprobs: int = 0):
+        """`token_logprobs` / `top_logprobs` (no counterpart in the reference; keywords, because DecodingResult keeps the
+        reference's fields): `run` returns `DetailedDecodingResult`s with, per token, the log-probability it was chosen
+        with, the entropy of the distribution it was chosen from and the `top_logprobs` (0 .. 8, implies `token_logprobs`)
+        most probable alternatives — of the edited and filtered distribution, written by the device-side greedy / sampling
+        loop as it goes (the host loop of a custom filter or Inference computes the same from its filtered logits).  With
+        best_of they follow the sample the ranker selects.  Not with beam search: ValueError.
+        `no_repeat_ngram_size` / `repetition_penalty` (no counterpart in the reference; keywords, because DecodingOptions
         keeps the reference's fields): repetition control over a row's SAMPLED tokens — timestamps included, prompt and
         prefix not, so text of the previous window stays repeatable; ids >= <|endoftext|> are never banned or penalised
         (NoRepeatNGram, RepetitionPenalty).  0 / 1.0 are off.  Greedy decoding and sampling apply both inside the
@@ -608,6 +668,11 @@ class DecodingTask:
                                   language=options.language or "en", task=options.task)
         self.tokenizer: Tokenizer = tokenizer
         self.options: DecodingOptions = self._verify_options(options)
+        self.token_logprobs, self.top_logprobs = check_token_stats(token_logprobs, top_logprobs)
+        if self.token_logprobs and options.beam_size is not None:
+            raise ValueError("token_logprobs / top_logprobs are not available with beam search (a winner's per-step scores "
+                             "are not kept)")
+        self._stats: Optional[Tuple[Tensor, Tensor, Optional[Tensor], Optional[Tensor]]] = None
 
         self.n_group: int = options.beam_size or options.best_of or 1
         self.n_ctx: int = model.dims.n_text_ctx
@@ -861,18 +926,27 @@ class DecodingTask:
                 task.set_phrases(self.phrases.device_arrays(dev), self.phrases.boost)
             if self.no_repeat_ngram_size or self.repetition_penalty != 1.0:     # likewise forgotten at reset
                 task.set_repetition(self.no_repeat_ngram_size, self.repetition_penalty)
+            if self.token_logprobs:              # likewise; the loop then returns the statistics buffers as well
+                task.set_token_stats(self.top_logprobs)
             if wait:
                 res = task.greedy(buf, params, self.sot_index, no_speech)
             else:
                 res = yield from self._await(task.greedy_begin(buf, params, self.sot_index, no_speech))
-            n, sum_logprobs, nsp = res
+            n, sum_logprobs, nsp = res[:3]
+            stats = [None if b is None else b[:, :n] for b in res[3]] if self.token_logprobs else None
             no_speech_probs = nsp.tolist() if nsp is not None else [np.nan] * n_rows
             if not ragged:
+                self._stats = stats
                 return buf[:, :n], sum_logprobs, no_speech_probs
             # row r holds n - lag tokens: right-align so that every row's sampled part starts at sample_begin
             out = torch.full((n_rows, n), tk.sot, dtype=torch.int64, device=dev)
             for r, lag in enumerate(row_lag):
                 out[r, lag:] = buf[r, : n - lag]
+            if stats is not None:                # the statistics are indexed by token column: the same shift
+                stats = [None if b is None else torch.cat([torch.zeros_like(b), b], dim=1) for b in stats]
+                stats = [None if b is None else torch.stack([b[r, n - lag: 2 * n - lag] for r, lag in enumerate(row_lag)])
+                         for b in stats]
+            self._stats = stats
             return out, sum_logprobs, no_speech_probs
         finally:
             self.inference.cleanup_caching()
@@ -935,6 +1009,7 @@ class DecodingTask:
         in_place = type(self.decoder) is GreedyDecoder
         if in_place:
             self.decoder._in_place = True           # this loop hands every returned `tokens` straight back (see _append)
+        step_stats, T0 = [], tokens.shape[1]
         try:
             for i in range(self.sample_len):
                 logits = self.inference.logits(tokens, audio_features)
@@ -946,6 +1021,8 @@ class DecodingTask:
                 for logit_filter in self.logit_filters:
                     logit_filter.apply(logits, tokens)
                 hip_steps = type(self.inference) is HipInference
+                if self.token_logprobs:          # the distribution the decoder is about to choose from
+                    filtered, ended = logits.float().clone(), tokens[:, -1] == self.tokenizer.eot
                 try:
                     tokens, completed = self.decoder.update(tokens, logits, sum_logprobs)
                 except ValueError:
@@ -955,6 +1032,8 @@ class DecodingTask:
                         timed_out = True
                         break
                     raise
+                if self.token_logprobs:
+                    step_stats.append(step_token_stats(filtered, tokens[:, -1], ended, self.top_logprobs))
                 if completed or tokens.shape[-1] > self.n_ctx:
                     break
                 # a time-out invalidates every later step of the window: look every 16 tokens (the loop synchronises with
@@ -968,6 +1047,13 @@ class DecodingTask:
             if in_place:
                 self.decoder._in_place = False
             self.inference.cleanup_caching()
+        if self.token_logprobs:                  # [rows][token column], like the device-side loop's buffers
+            def columns(j, fill, dtype):
+                head = torch.full((n_batch, T0) + ((self.top_logprobs,) if j >= 2 else ()), fill, dtype=dtype, device=tokens.device)
+                return torch.cat([head] + [st[j][:, None] for st in step_stats], dim=1)
+            self._stats = [columns(0, 0.0, torch.float32), columns(1, 0.0, torch.float32),
+                           columns(2, -1, torch.int64) if self.top_logprobs else None,
+                           columns(3, float("-inf"), torch.float32) if self.top_logprobs else None]
         return tokens, sum_logprobs, no_speech_probs, timed_out
 
     @torch.no_grad()
@@ -985,6 +1071,7 @@ class DecodingTask:
         """`run` as a generator (resume it under torch.no_grad(), as `run_interleaved` does: a grad-mode context must not be
         held across a yield, several generators share the thread)"""
         self.decoder.reset()
+        self._stats = None
         tokenizer: Tokenizer = self.tokenizer
         n_audio: int = mel.shape[0]
 
@@ -1009,6 +1096,7 @@ class DecodingTask:
         no_speech_probs = no_speech_probs[:: self.n_group]
         assert audio_features.shape[0] == len(no_speech_probs) == n_audio
 
+        n_columns = tokens.shape[-1]             # token columns the loop filled (every row, ragged ones right-aligned)
         tokens = tokens.reshape(n_audio, self.n_group, -1)
         sum_logprobs = sum_logprobs.reshape(n_audio, self.n_group)
         tokens, sum_logprobs = self.decoder.finalize(tokens, sum_logprobs)
@@ -1027,12 +1115,33 @@ class DecodingTask:
         fields = (texts, languages, tokens, audio_features, avg_logprobs, no_speech_probs)
         if len(set(map(len, fields))) != 1:
             raise RuntimeError(f"inconsistent result lengths: {list(map(len, fields))}")
-        return [
+        results = [
             DecodingResult(audio_features=features, language=language, tokens=tokens, text=text,
                            avg_logprob=avg_logprob, no_speech_prob=no_speech_prob,
                            temperature=self.options.temperature, compression_ratio=compression_ratio(text))
             for text, language, tokens, features, avg_logprob, no_speech_prob in zip(*fields)
         ]
+        if self.token_logprobs:
+            results = self._with_token_stats(results, selected, n_columns)
+        return results
+
+    def _with_token_stats(self, results: List[DecodingResult], selected: Sequence[int], n_columns: int):
+        """the rows the ranker selected, cut like their tokens: one entry per token, then the closing <|endoftext|>'s where a
+        step produced it (a row that ran out of `sample_len` has none)"""
+        if self._stats is None:
+            raise RuntimeError("the decode loop returned no per-token statistics")
+        lp, ent, top_t, top_v = [None if b is None else b.cpu() for b in self._stats]
+        out = []
+        for a, (res, i) in enumerate(zip(results, selected)):
+            row = a * self.n_group + int(i)
+            end = min(self.sample_begin + len(res.tokens) + 1, n_columns, lp.shape[1])
+            cols = slice(self.sample_begin, end)
+            out.append(DetailedDecodingResult(
+                **{f.name: getattr(res, f.name) for f in dataclass_fields(DecodingResult)},
+                token_logprobs=lp[row, cols].tolist(), token_entropies=ent[row, cols].tolist(),
+                top_tokens=top_t[row, cols].tolist() if top_t is not None else [],
+                top_logprobs=top_v[row, cols].tolist() if top_v is not None else []))
+        return out
 
 
 @torch.no_grad()
@@ -1043,7 +1152,8 @@ def decode(model: "Whisper", mel: Tensor, options: DecodingOptions = DecodingOpt
     parameter list stays the reference's plus `prompts`): a phrase list to prefer, a `PhraseList` or a plain list of strings
     (see DecodingTask); the other keywords replace fields of `options`."""
     phrases = kwargs.pop("phrases", None)
-    repetition = {k: kwargs.pop(k) for k in ("no_repeat_ngram_size", "repetition_penalty") if k in kwargs}
+    repetition = {k: kwargs.pop(k) for k in ("no_repeat_ngram_size", "repetition_penalty", "token_logprobs", "top_logprobs")
+                  if k in kwargs}
     single = mel.ndim == 2
     if single:
         mel = mel.unsqueeze(0)
@@ -1331,7 +1441,8 @@ def coalesce_batches(rows: Sequence[int], chain_rows: Optional[int]) -> List[Lis
 
 def decode_many(model: "Whisper", mels: Sequence[Tensor], options: DecodingOptions = DecodingOptions(), in_flight: int = 3,
                 chain_rows: Optional[int] = 24, phrases: Optional[Union[PhraseList, Sequence]] = None,
-                no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, **kwargs) -> List[List[DecodingResult]]:
+                no_repeat_ngram_size: int = 0, repetition_penalty: float = 1.0, token_logprobs: bool = False,
+                top_logprobs: int = 0, **kwargs) -> List[List[DecodingResult]]:
     """`decode(model, mel, options)` for every batch of `mels` — each a (B, n_mels, 3000) tensor, or raw (B, 480000) audio (its
     log-mel is then taken here, per batch: audio.py:155 clamps against the maximum over the tensor it is given) — scheduled for
     throughput; returns the per-batch result lists in order.  No counterpart in the reference.  Two levers:
@@ -1345,8 +1456,10 @@ def decode_many(model: "Whisper", mels: Sequence[Tensor], options: DecodingOptio
       * `in_flight`: up to this many chains are decoded at once, each on a HIP stream of its own, all driven from the calling
         thread (`run_interleaved`): chains of few rows leave the chip idle between their dependent launches and fill each other's
         gaps.  Chains of 16+ rows of a large model gain little from it.
-    `phrases`: one phrase list for all batches (see DecodingTask); `no_repeat_ngram_size` / `repetition_penalty` likewise."""
+    `phrases`: one phrase list for all batches (see DecodingTask); `no_repeat_ngram_size` / `repetition_penalty` and
+    `token_logprobs` / `top_logprobs` likewise."""
     repetition = dict(zip(("no_repeat_ngram_size", "repetition_penalty"), check_repetition(no_repeat_ngram_size, repetition_penalty)))
+    repetition.update(zip(("token_logprobs", "top_logprobs"), check_token_stats(token_logprobs, top_logprobs)))
     if kwargs:
         options = replace(options, **kwargs)
     if phrases is not None and not isinstance(phrases, PhraseList):      # compiled once, shared by every chain

@@ -98,6 +98,26 @@ class BeamParams(C.Structure):
 
 
 # name -> (restype, argtypes); also the list the CPU-only symbol test walks
+class TokenStats(C.Structure):
+    """wh_token_stats: where the device-side greedy / sampling loop writes its per-token statistics (device buffers)"""
+    _fields_ = [
+        ("token_logprobs", C.c_void_p), ("entropy", C.c_void_p), ("top_k", C.c_int32),
+        ("top_tokens", C.c_void_p), ("top_logprobs", C.c_void_p), ("stride", C.c_int64),
+    ]
+
+
+TOKEN_STATS_MAX_TOP = 8
+
+
+class TokenStatBuffers(NamedTuple):
+    """what a loop with statistics returns beside its results: indexed like the token buffer, [row][column] (+ [j < top_k]);
+    columns no step wrote hold 0, 0, (-1, -inf)"""
+    token_logprobs: torch.Tensor
+    entropy: torch.Tensor
+    top_tokens: Optional[torch.Tensor]
+    top_logprobs: Optional[torch.Tensor]
+
+
 SIGNATURES = {
     "wh_abi_version": (C.c_int, []),
     "wh_status_string": (C.c_char_p, [C.c_int]),
@@ -128,6 +148,7 @@ SIGNATURES = {
     "wh_task_set_lag": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "wh_task_set_phrases": (C.c_int, [C.c_void_p, C.POINTER(Phrases), C.c_void_p]),
     "wh_task_set_repetition": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
+    "wh_task_set_token_stats": (C.c_int, [C.c_void_p, C.POINTER(TokenStats), C.c_void_p]),
     "wh_task_position": (C.c_int, [C.c_void_p]),
     "wh_task_info": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "wh_task_greedy": (C.c_int, [C.c_void_p, C.POINTER(GreedyParams), C.c_void_p, C.c_int64, C.c_int, C.c_int,
@@ -775,6 +796,7 @@ class HipTask:
         with self._call():
             check(lib().wh_task_reset(self.handle, stream_ptr(self.stream)), "wh_task_reset")
         self._phrase_arrays = None
+        self._token_stats = None
 
     def set_phrases(self, arrays: Optional[Sequence[torch.Tensor]], boost: float = 0.0):
         """phrase list of the device-side greedy / sampling loop (wh_task_set_phrases): `arrays` = the trie's CSR arrays
@@ -804,6 +826,43 @@ class HipTask:
         with self._call():
             check(lib().wh_task_set_repetition(self.handle, int(no_repeat_ngram_size), float(repetition_penalty),
                                                stream_ptr(self.stream)), "wh_task_set_repetition")
+
+    def set_token_stats(self, top_k: Optional[int] = 0):
+        """per-token statistics of the device-side greedy / sampling loop (wh_task_set_token_stats): the log-probability of
+        every chosen token, the entropy of the distribution it was chosen from and, with top_k > 0, its top_k most probable
+        alternatives.  `greedy` / `greedy_begin` then allocate the buffers next to their token buffer (same row stride) and
+        return them as a fourth result, a `TokenStatBuffers`.  None clears, and so does `reset`."""
+        if top_k is None:
+            with self._call():
+                check(lib().wh_task_set_token_stats(self.handle, None, stream_ptr(self.stream)), "wh_task_set_token_stats")
+            self._token_stats = None
+            return
+        if not (0 <= int(top_k) <= TOKEN_STATS_MAX_TOP):
+            raise ValueError(f"top_k must lie in 0..{TOKEN_STATS_MAX_TOP}")
+        self._token_stats = int(top_k)
+
+    def _stat_buffers(self, tokens: torch.Tensor) -> Optional["TokenStatBuffers"]:
+        """the statistics buffers of one loop over `tokens`, filled on the caller's stream (call it before the task's stream
+        waits for the caller's)"""
+        k = getattr(self, "_token_stats", None)
+        if k is None:
+            return None
+        R, S, dev = self.n_rows, tokens.stride(0), tokens.device
+        return TokenStatBuffers(
+            torch.zeros(R, S, dtype=torch.float32, device=dev), torch.zeros(R, S, dtype=torch.float32, device=dev),
+            torch.full((R, S, k), -1, dtype=torch.int32, device=dev) if k else None,
+            torch.full((R, S, k), float("-inf"), dtype=torch.float32, device=dev) if k else None)
+
+    def _stat_set(self, buf: Optional["TokenStatBuffers"]):
+        """hand them to the task, for the loop begun next (inside the task's stream order)"""
+        if buf is None:
+            return
+        p = TokenStats(token_logprobs=buf.token_logprobs.data_ptr(), entropy=buf.entropy.data_ptr(), top_k=self._token_stats,
+                       top_tokens=_ptr(buf.top_tokens), top_logprobs=_ptr(buf.top_logprobs), stride=buf.entropy.stride(0))
+        check(lib().wh_task_set_token_stats(self.handle, C.byref(p), stream_ptr(self.stream)), "wh_task_set_token_stats")
+        for b in buf:
+            if b is not None:
+                b.record_stream(self.stream)
 
     def set_lag(self, lag: Optional[Sequence[int]]):
         """ragged prompts: row r's sequence is the longest row's shifted left by lag[r] (include/whisper_hip.h)"""
@@ -848,17 +907,20 @@ class HipTask:
 
     def greedy(self, tokens: torch.Tensor, params: GreedyParams, sot_index: int, no_speech_token: int):
         """tokens: int64 [n_rows][>= sample_begin + max_steps], initial tokens in the first columns.
-        Returns (n_tokens, sum_logprobs[n_rows], no_speech_probs[n_rows] | None)."""
+        Returns (n_tokens, sum_logprobs[n_rows], no_speech_probs[n_rows] | None), and after `set_token_stats` a
+        `TokenStatBuffers` as a fourth element."""
         assert tokens.is_cuda and tokens.dtype == torch.int64 and tokens.stride(1) == 1
         dev = tokens.device
         sum_lp = torch.empty(self.n_rows, dtype=torch.float32, device=dev)
         nsp = torch.empty(self.n_rows, dtype=torch.float32, device=dev) if no_speech_token >= 0 else None
         n_out = C.c_int32(0)
+        stats = self._stat_buffers(tokens)
         with self._call():
+            self._stat_set(stats)
             check(lib().wh_task_greedy(self.handle, C.byref(params), tokens.data_ptr(), tokens.stride(0), sot_index,
                                        no_speech_token, sum_lp.data_ptr(), _ptr(nsp), C.byref(n_out),
                                        stream_ptr(self.stream)), "wh_task_greedy")
-        return n_out.value, sum_lp, nsp
+        return (n_out.value, sum_lp, nsp) if stats is None else (n_out.value, sum_lp, nsp, stats)
 
     def beam(self, tokens: torch.Tensor, params: BeamParams, sot_index: int, no_speech_token: int):
         """tokens: int64 [2][n_rows][>= sample_begin + max_steps + 1], initial tokens in the first columns of [0].
@@ -891,10 +953,14 @@ class HipTask:
         dev = tokens.device
         sum_lp = torch.empty(self.n_rows, dtype=torch.float32, device=dev)
         nsp = torch.empty(self.n_rows, dtype=torch.float32, device=dev) if no_speech_token >= 0 else None
+        stats = self._stat_buffers(tokens)
         pend = PendingLoop(self, (tokens, params, sum_lp, nsp), lambda n: (n, sum_lp, nsp))
+        if stats is not None:
+            pend = PendingLoop(self, (tokens, params, sum_lp, nsp, stats), lambda n: (n, sum_lp, nsp, stats))
         with torch.cuda.device(self.model.device):
             pend.caller = torch.cuda.current_stream(self.model.device)
             self.stream.wait_stream(pend.caller)
+            self._stat_set(stats)
             check(lib().wh_task_greedy_begin(self.handle, C.byref(params), tokens.data_ptr(), tokens.stride(0), sot_index,
                                              no_speech_token, sum_lp.data_ptr(), _ptr(nsp), stream_ptr(self.stream)),
                   "wh_task_greedy_begin")

@@ -107,9 +107,11 @@ def transcribe_sharded(model, audios: Sequence[Any], dist=None, *, batch_size: i
     rank 0 returns the result dicts in input order, other ranks None.  All inputs must be of one kind (arrays or
     paths) for the costs to be comparable.  `device_ingest` (True / "decode"): every rank loads its files on its own GPU (transcribe_batch).
     `phrases` / `phrase_boost` among the keywords: one phrase list for all files, compiled on every rank (transcribe_batch);
-    `no_repeat_ngram_size` / `repetition_penalty` among them as well: repetition control on every rank (transcribe)."""
-    from .decoding import check_repetition
+    `no_repeat_ngram_size` / `repetition_penalty` among them as well: repetition control on every rank (transcribe);
+    `token_logprobs` / `top_logprobs` likewise: per-token statistics in every segment of every rank's results."""
+    from .decoding import check_repetition, check_token_stats
     check_repetition(kwargs.get("no_repeat_ngram_size", 0), kwargs.get("repetition_penalty", 1.0))     # before any rank starts work
+    check_token_stats(kwargs.get("token_logprobs", False), kwargs.get("top_logprobs", 0))
     from .transcribe import transcribe_batch
     costs = [_audio_cost(a) for a in audios]
     if device_ingest:

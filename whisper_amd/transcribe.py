@@ -88,15 +88,24 @@ def _pop_repetition(options: dict) -> dict:
     """take `no_repeat_ngram_size` / `repetition_penalty` out of a keyword dict (no DecodingOptions fields either) and check
     them (ValueError); returns the keywords for `model.decode` — none while both are off, so that the call is then the one
     made before the options existed"""
-    from .decoding import check_repetition
+    from .decoding import check_repetition, check_token_stats
     n, p = check_repetition(options.pop("no_repeat_ngram_size", 0), options.pop("repetition_penalty", 1.0))
-    return {} if (n == 0 and p == 1.0) else {"no_repeat_ngram_size": n, "repetition_penalty": p}
+    out = {} if (n == 0 and p == 1.0) else {"no_repeat_ngram_size": n, "repetition_penalty": p}
+    # `token_logprobs` / `top_logprobs` (per-token statistics, decoding.py DetailedDecodingResult) travel the same way
+    lp, k = check_token_stats(options.pop("token_logprobs", False), options.pop("top_logprobs", 0))
+    if lp:
+        out.update(token_logprobs=True, top_logprobs=k)
+    return out
 
 
 def _check_repetition(kwargs: dict) -> None:
     """argument errors of the two options before any work of a batched call (they stay among the keywords)"""
-    from .decoding import check_repetition
+    from .decoding import check_repetition, check_token_stats
     check_repetition(kwargs.get("no_repeat_ngram_size", 0), kwargs.get("repetition_penalty", 1.0))
+    check_token_stats(kwargs.get("token_logprobs", False), kwargs.get("top_logprobs", 0))
+    if kwargs.get("token_logprobs") or kwargs.get("top_logprobs"):
+        if kwargs.get("beam_size") is not None:
+            raise ValueError("token_logprobs / top_logprobs are not available with beam search")
 
 
 def _compile_phrases(model: "Whisper", kwargs: dict) -> None:
@@ -251,14 +260,29 @@ class _Transcriber:
         last_speech_timestamp = 0.0
         threshold = self.hallucination_silence_threshold
 
-        def make_segment(*, seek_at: int, start: float, end: float, tokens: torch.Tensor, result: DecodingResult) -> dict:
+        def make_segment(*, seek_at: int, start: float, end: float, tokens: torch.Tensor, result: DecodingResult,
+                         begin: int = 0) -> dict:
             ids = tokens.tolist()
-            return {
+            segment = {
                 "seek": seek_at, "start": start, "end": end,
                 "text": tokenizer.decode([t for t in ids if t < tokenizer.eot]),
                 "tokens": ids, "temperature": result.temperature, "avg_logprob": result.avg_logprob,
                 "compression_ratio": result.compression_ratio, "no_speech_prob": result.no_speech_prob,
             }
+            if stat_keys:
+                # per-token statistics, cut where the tokens are cut (`begin`: the piece's position in the window's tokens);
+                # the closing <|endoftext|>'s entry belongs to no segment
+                cut = slice(begin, begin + len(ids))
+                segment["token_logprobs"] = list(result.token_logprobs[cut])
+                segment["token_entropies"] = list(result.token_entropies[cut])
+                if "top_logprobs" in stat_keys:
+                    segment["top_logprobs"] = [[[int(t), float(v)] for t, v in zip(tt, vv)]
+                                               for tt, vv in zip(result.top_tokens[cut], result.top_logprobs[cut])]
+            return segment
+
+        stat_keys: Tuple[str, ...] = ()
+        if self.repetition.get("token_logprobs"):
+            stat_keys = ("token_logprobs", "token_entropies") + (("top_logprobs",) if self.repetition.get("top_logprobs") else ())
 
         with tqdm.tqdm(total=content_frames, unit="frames", disable=self.verbose is not False) as pbar:
             while clip_idx < len(seek_clips):
@@ -310,7 +334,7 @@ class _Transcriber:
                         t_end = piece[-1].item() - tokenizer.timestamp_begin
                         current_segments.append(make_segment(
                             seek_at=seek, start=time_offset + t_start * time_precision,
-                            end=time_offset + t_end * time_precision, tokens=piece, result=result))
+                            end=time_offset + t_end * time_precision, tokens=piece, result=result, begin=begin))
                         begin = cut
                     if single_timestamp_ending:
                         seek += segment_size      # nothing spoken after the last timestamp
@@ -397,6 +421,8 @@ class _Transcriber:
                         segment["text"] = ""
                         segment["tokens"] = []
                         segment["words"] = []
+                        for key in stat_keys:          # aligned with "tokens"
+                            segment[key] = []
 
                 base = len(all_segments)
                 all_segments.extend({"id": base + i, **segment} for i, segment in enumerate(current_segments))
