@@ -284,10 +284,15 @@ __global__ __launch_bounds__(FW * 64, WH_FLASH_WAVES_PER_SIMD) void attn_flash_f
     half8v pf[2][2];
     if constexpr (PRESCALED) {
       // mx is already relative to the reference (the accumulators started at -m_run); key 0 of every tile is valid,
-      // so it is finite.  The first tile always sets the reference.
+      // so it is finite.  The first tile always sets the reference: delta = mx, of either sign.  The factor on the
+      // accumulators is exp2 of a clamped argument, never exp2(-mx) as such: nothing has been accumulated on the first tile,
+      // so any finite factor leaves oacc and l_run at 0, but where every score of a query's first tile lies below -128
+      // exp2(-mx) is +inf, and 0 * inf made that query NaN for the rest of the launch.  After the first tile delta is the
+      // clamped value anyway.  (`kt == 0 ? 0.f : exp2(-delta)` says the same; this form adds one v_max to the branch and leaves the
+      // register allocation of the loop as it was: profiles/flash_range_regs.txt.)
       if (kt == 0 || __any(mx > DEFER)) {            // wave-uniform: rare after the first tiles
         const float delta = kt == 0 ? mx : fmaxf(mx, 0.f);
-        const float alpha = __builtin_amdgcn_exp2f(-delta);
+        const float alpha = __builtin_amdgcn_exp2f(-fmaxf(mx, 0.f));
 #pragma unroll
         for (int i = 0; i < 16; ++i) { oacc[0][i] *= alpha; oacc[1][i] *= alpha; sacc[0][i] -= delta; sacc[1][i] -= delta; }
         l_run *= alpha;
